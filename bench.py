@@ -1,12 +1,19 @@
 """PLDepth training-step throughput on MI355X (BASELINE.json metric: images/s at 448x448,
 ranking_size=5, ff_effnet, per-GPU batch 32, Info sampler, Adam-AMSGrad; synthetic data).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 A step = GPU ranking sampler + ff_effnet forward + ListMLE + backward + (RCCL all-reduce) +
 Adam-AMSGrad + filter refresh, on a resident synthetic batch, replayed from hipGraphs. Rank 0
-prints one JSON line. See DESIGN.md §Measurement for the roofline and cpu_baseline definitions.
+prints one JSON line.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the line (throughput, ms_per_step, loss, configuration).
+--full adds everything else after the timed region: the conv roofline (eager profiling steps,
+graph replays of the dominant kernel, byte floor, committed PMC profiles), the replicas'
+parameter check at N > 1, the loss delta against the fp64 oracle, the cfg3 / cfg5 workloads and
+the CPU baseline. See DESIGN.md §Measurement for the roofline and cpu_baseline definitions.
 """
 import argparse
 import json
@@ -50,6 +57,31 @@ def synthetic_batch(B, H, W, seed):
         gt[b] = np.round(255 * f).astype(np.float32) / np.float32(255)
     mask = (rng.random((B, H, W)) < 0.9).astype(np.float32)
     return x, gt, mask
+
+
+DUMP_ARRAY_BYTES = 28 << 20  # per dumped array; the five arrays stay under 64 MB in all
+
+
+def dump_outputs(trainer, out_dir):
+    """What the last timed step left for its caller, as out_dir/<name>.npy (float32): the step's
+    ListMLE loss, the rankings the sampler drew, the prediction, the parameters after the Adam
+    update and the BN moving statistics. An array over DUMP_ARRAY_BYTES is written as a fixed
+    sample of its flattened elements (sorted indices from default_rng(0), the same for every run
+    at the same shape). Call right after the timed steps, before anything else steps the
+    trainer."""
+    trainer.synchronize()
+    torch.cuda.synchronize()
+    eng = trainer.engine
+    arrays = {"loss": trainer.loss, "y_true": trainer.y_true, "pred": eng.act["pred"],
+              "params": eng.params.buf, "bn_stats": eng.stats.buf}
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_ARRAY_BYTES // 4
+    for name, t in arrays.items():
+        v = t.detach().float().cpu().numpy()
+        if v.size > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, v.size, cap))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, np.float32))
 
 
 def profile_conv(trainer, lr, replays=None):
@@ -665,12 +697,23 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo rehearses the "
                          "path with ranks sharing one GPU)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (loss, "
+                         "rankings, prediction, updated parameters, BN moving statistics) as "
+                         "DIR/<name>.npy (float32, under 64 MB in all; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the "
+                         "headline: conv roofline, replicas' parameter check (N > 1), loss delta "
+                         "vs the fp64 oracle, the cfg3 / cfg5 workloads, the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU legs (cpu_baseline timing and the loss-delta check)")
+                    help="with --full: skip the CPU legs (cpu_baseline timing and the loss-delta "
+                         "check)")
     ap.add_argument("--no-loss-parity", action="store_true",
-                    help="skip the ListMLE loss delta vs the fp64 oracle (loss_parity)")
+                    help="with --full: skip the ListMLE loss delta vs the fp64 oracle "
+                         "(loss_parity)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the cfg3 (ff_resnet) and cfg5 (L=64, R=1000) lines (1 GPU only)")
+                    help="with --full: skip the cfg3 (ff_resnet) and cfg5 (L=64, R=1000) lines "
+                         "(1 GPU only)")
     ap.add_argument("--conv-math", default="auto", choices=["auto", "mixed", "bf16x3", "fp32"],
                     help="conv arithmetic policy (kernels.conv_policy): auto = decoder bf16x3, "
                          "encoder bf16x3 where the BN sees >= 4096 values per channel (all of "
@@ -703,6 +746,30 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     from pldepth_amd.dp import exit_on_failure
     exit_on_failure(lambda: run(a, world), world)
+
+
+def step_roofline(a, tr, value, world, workload):
+    """--full: the roofline object of the line. Dominant conv kernel + conv family: algorithmic
+    FLOPs / measured duration (HIP events on the trainer's stream, one eager step), the dominant
+    kernel's graph replays, the step's byte floor (one more eager step) and the committed
+    profiles of the same workload."""
+    log("profiling")
+    replays = []
+    recs = profile_conv(tr, 0.01, replays)
+    flops_img = tr.engine.conv_flops_per_image()
+    roof = conv_roofline(recs, a.traffic_profile)
+    replay_dominant(tr, replays, roof)
+    del replays
+    attach_traffic(roof, a.traffic_profile, workload)
+    roof["step_frac"] = round(value / world * flops_img / 1e12 / roof["family"]["peak"], 4)
+    fam, total = step_byte_floor(tr, 0.01)
+    roof["step_bytes_algorithmic"] = {
+        "total": total, "by_family": dict(sorted(fam.items(), key=lambda kv: -kv[1])),
+        "definition": "per launch, every distinct tensor the call is handed counted once (inputs "
+                      "read once, outputs written once), summed over one step's launches"}
+    attach_step_traffic(roof, a.step_traffic_profile, workload)
+    attach_graph_frac(roof, a.graph_profile, workload)
+    return roof
 
 
 def run(a, world):
@@ -746,8 +813,12 @@ def run(a, world):
                              world, pg, graph=not a.no_graph)
     loss = tr.loss_value()
     value = world * B * a.steps / elapsed
+    if a.dump_outputs and rank == 0:
+        dump_outputs(tr, a.dump_outputs)
+    workload = (f"{a.model} train step {H}x{H}, per-GPU batch {B}, ranking_size {L}, "
+                f"rankings_per_image {R}, sampler {tr.strategy}, Adam-AMSGrad")
     dist_check = None
-    if world > 1:
+    if world > 1 and a.full:
         # every replica applied the same all-reduced gradients: parameters equal bit for bit
         from pldepth_amd import dp
         same, sums = dp.replicas_identical(tr.engine.params.buf, pg)
@@ -758,26 +829,7 @@ def run(a, world):
                       # (trainer dp_overlap; PLD_DP_OVERLAP=0: after the backward)
                       "dp_overlap": tr.dp_overlap}
 
-    # dominant conv kernel + conv family: algorithmic FLOPs / measured duration (HIP events on
-    # the trainer's stream, one eager step)
-    log(f"timed: {1e3 * elapsed / a.steps:.3f} ms/step; profiling")
-    replays = []
-    recs = profile_conv(tr, 0.01, replays)
-    flops_img = tr.engine.conv_flops_per_image()
-    roof = conv_roofline(recs, a.traffic_profile)
-    replay_dominant(tr, replays, roof)
-    del replays
-    workload = (f"{a.model} train step {H}x{H}, per-GPU batch {B}, ranking_size {L}, "
-                f"rankings_per_image {R}, sampler {tr.strategy}, Adam-AMSGrad")
-    attach_traffic(roof, a.traffic_profile, workload)
-    roof["step_frac"] = round(value / world * flops_img / 1e12 / roof["family"]["peak"], 4)
-    fam, total = step_byte_floor(tr, 0.01)
-    roof["step_bytes_algorithmic"] = {
-        "total": total, "by_family": dict(sorted(fam.items(), key=lambda kv: -kv[1])),
-        "definition": "per launch, every distinct tensor the call is handed counted once (inputs "
-                      "read once, outputs written once), summed over one step's launches"}
-    attach_step_traffic(roof, a.step_traffic_profile, workload)
-    attach_graph_frac(roof, a.graph_profile, workload)
+    log(f"timed: {1e3 * elapsed / a.steps:.3f} ms/step")
     out = {
         "metric": "images/sec (448x448, ranking_size=5) at 1/2/4/8 GPU; ListMLE loss delta vs TF2",
         "value": round(value, 3),
@@ -800,18 +852,19 @@ def run(a, world):
                    "gpus_visible": torch.cuda.device_count()},
         "conv_math": {"policy": a.conv_math, "encoder": tr.engine.enc_math,
                       "decoder": tr.engine.dec_math},
-        "roofline": roof,
+        **({"roofline": step_roofline(a, tr, value, world, workload)} if a.full else {}),
         "loss": loss,
         "distributed": dist_check,
         "schedules": sched,
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.no_loss_parity:
+    # a plain run only writes --tune's table and prints the line from here on
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.no_loss_parity:
         log("loss parity vs the fp64 oracle")
         par = loss_parity(tr, 0.01)
         out["loss_delta"] = par["loss_delta"]
         out["loss_parity"] = par
     del tr
-    if world == 1 and not a.no_extra_configs and a.model == "ff_effnet" and H == 448:
+    if a.full and world == 1 and not a.no_extra_configs and a.model == "ff_effnet" and H == 448:
         extra = {}
         for key, model, el, er in EXTRA_CONFIGS:
             t2, el_s = run_config(model, H, B, el, er, a.sampling_type, a.steps, a.warmup,
@@ -827,7 +880,7 @@ def run(a, world):
     if a.tune and rank == 0:
         K.save_tile_cache(a.tune)
         out["schedules"]["written"] = a.tune
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         log("cpu baseline")
         out["cpu_baseline"] = cpu_baseline(H, H, L, R, a.model)
     if rank == 0:

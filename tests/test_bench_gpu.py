@@ -30,7 +30,7 @@ def test_bench_world2_gloo_line(cuda):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--backend", "gloo", "--size", "224", "--batch", "8", "--no-extra-configs",
+           "--backend", "gloo", "--size", "224", "--batch", "8", "--full", "--no-extra-configs",
            "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -24,9 +24,9 @@ if [ "$2" != "--no-tests" ]; then
   if [ $TEST_RC -ne 0 ] && [ $TEST_RC -ne 1 ]; then exit $TEST_RC; fi
 fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 python3 $R/bench.py > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 tail -c 400 $O/bench.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-loss-parity --no-extra-configs > $O/trace.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-loss-parity --no-extra-configs > $O/trace.log 2>&1 || exit 1
 DB=$(ls $O/trace/*/run_results.db 2>/dev/null | head -1)
 [ -z "$DB" ] && DB=$(ls $O/trace/run_results.db 2>/dev/null | head -1)
 python3 $R/tools/kstats.py $DB --marker adam_amsgrad_dev_kernel --steps 10 --skip 1 --csv $O/kernel_stats.csv --top 70 > $O/kstats.txt || exit 1

@@ -7,7 +7,7 @@ STEPS=${2:-8}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- python3 $R/bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --no-extra-configs > $O/bench.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- python3 $R/bench.py --steps $STEPS --warmup 3 --full --no-cpu-baseline --no-extra-configs > $O/bench.log 2>&1 || exit 1
 DB=$(ls $O/trace/*/run_results.db 2>/dev/null | head -1)
 [ -z "$DB" ] && DB=$(ls $O/trace/run_results.db 2>/dev/null | head -1)
 python3 $R/tools/kstats.py $DB --marker adam_amsgrad_dev_kernel --steps $STEPS --skip 1 --csv $O/kernel_stats.csv --top 60 > $O/kstats.txt

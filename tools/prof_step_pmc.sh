@@ -4,7 +4,7 @@ MODEL=${1:-ff_effnet}
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/pmc_step
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --model $MODEL --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --no-graph"
+B="python3 $R/bench.py --model $MODEL --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra-configs --no-graph"
 timeout -k 10 200 $B > $R/gpurun_out/pmc_step/warm.log 2>&1
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $R/gpurun_out/pmc_step/fetch -o run --output-format csv -- $B > $R/gpurun_out/pmc_step/fetch.log 2>&1
 timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $R/gpurun_out/pmc_step/write -o run --output-format csv -- $B > $R/gpurun_out/pmc_step/write.log 2>&1
