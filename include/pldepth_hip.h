@@ -546,6 +546,50 @@ int pld_dcg_ratio(const float* pred, const float* gt, int n, int64_t hw, const i
                   int list_size, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depth-edge metrics: pldepth/active_learning/metrics.py:123-144
+ * depth_edge_metric and preprocess_utils.py:4-13 auto_canny. The OpenCV calls the reference
+ * makes there (cv2.normalize, cv2.Canny, cv2.distanceTransform) are restated as kernels, one
+ * entry point per stage, each for a batch of n images. u8 maps are [n][h][w] bytes.
+ * The Canny entry points take maps of at most PLD_EDGE_MAX_DIM x PLD_EDGE_MAX_DIM pixels (the
+ * hysteresis keeps one image's label bits in LDS) and return PLD_ERR_UNSUPPORTED above that.
+ * ------------------------------------------------------------------------------------------ */
+#define PLD_EDGE_MAX_DIM 512
+/* metrics.py:124-125 cv2.normalize(x, None, 0, 255, NORM_MINMAX).astype(np.uint8) over each
+ * image of hw floats: scale = 255 / (max - min) in double (0 when max - min <= DBL_EPSILON),
+ * shift = -min * scale, (float)(x * scale + shift) truncated to [0, 255].
+ * ws >= pld_minmax_u8_workspace_size(n). */
+size_t pld_minmax_u8_workspace_size(int n);
+int pld_minmax_u8(const float* x, int n, int64_t hw, uint8_t* out_u8, void* ws, void* stream);
+/* cv2.Canny(img, lo, hi) (preprocess_utils.py:11): aperture 3, L1 gradient, border replicated;
+ * edges = 255 on every pixel that passes non-maximum suppression with |dx| + |dy| > hi and on
+ * every such pixel above lo that is 8-connected to one of those through such pixels, else 0.
+ * sweeps (may be NULL): [n] number of passes the hysteresis ran per image, at most h * w.
+ * ws >= pld_canny_workspace_size(n, h, w). */
+size_t pld_canny_workspace_size(int n, int h, int w);
+int pld_canny_u8(const uint8_t* img_u8, int n, int h, int w, int lo, int hi, uint8_t* edges_u8,
+                 int32_t* sweeps, void* ws, void* stream);
+/* preprocess_utils.py:4-13 auto_canny: v = np.median(img) from a 256-bin histogram,
+ * thr_out[i] = {int(max(0, lo_factor * v)), int(min(255, hi_factor * v))} in double with
+ * lo_factor = 1 - sigma and hi_factor = 1 + sigma formed by the caller, then pld_canny_u8 with
+ * each image's own thresholds. Same workspace and limits as pld_canny_u8. */
+int pld_auto_canny_u8(const uint8_t* img_u8, int n, int h, int w, double lo_factor,
+                      double hi_factor, int32_t* thr_out, uint8_t* edges_u8, int32_t* sweeps,
+                      void* ws, void* stream);
+/* metrics.py:129-133 cv2.distanceTransform(mask, DIST_L2, 3) followed by e[e > max_dist] = 0:
+ * at non-zero pixels the 3x3 chamfer distance (16.16 fixed point, 62587 per edge step, 89738
+ * per diagonal step, / 65536 as fp32) to the nearest zero pixel inside the image, 0 where it
+ * exceeds max_dist or no zero pixel exists; 0 at zero pixels. max_dist up to 10 (a search
+ * radius of 10 pixels; PLD_ERR_UNSUPPORTED above). */
+int pld_chamfer_dt3(const uint8_t* mask_u8, int n, int h, int w, float max_dist, float* out,
+                    void* stream);
+/* metrics.py:129-144 from the two edge maps (0 / non-zero), without the distance maps:
+ * out[i] = {sum(dt(gt) on op's edges) / #op edges, sum(dt(op) on gt's edges) / #gt edges} =
+ * {depth_boundary_error, completeness_error}, dt as pld_chamfer_dt3 with max_dist 10, summed in
+ * 64-bit fixed point; a map without edges gives 0.0 / 0.0 = nan like the reference. */
+int pld_depth_edge_metric(const uint8_t* edges_op, const uint8_t* edges_gt, int n, int h, int w,
+                          double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * hipGraph capture of a whole stream-ordered step (replaces Keras' per-op dispatch)
  * ------------------------------------------------------------------------------------------ */
 int pld_graph_begin(void* stream);

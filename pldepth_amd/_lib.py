@@ -17,6 +17,7 @@ I32 = C.c_int
 I64 = C.c_int64
 U64 = C.c_uint64
 F32 = C.c_float
+F64 = C.c_double
 SZ = C.c_size_t
 
 
@@ -131,6 +132,13 @@ _SIGS = {
     "pld_resize_nearest": (I32, [P, I32, I32, I32, I32, I32, I32, P, P]),
     "pld_ordinal_error": (I32, [P, P, I32, I64, P, P, I32, P, P]),
     "pld_dcg_ratio": (I32, [P, P, I32, I64, P, I32, P, P]),
+    "pld_minmax_u8_workspace_size": (SZ, [I32]),
+    "pld_minmax_u8": (I32, [P, I32, I64, P, P, P]),
+    "pld_canny_workspace_size": (SZ, [I32, I32, I32]),
+    "pld_canny_u8": (I32, [P, I32, I32, I32, I32, I32, P, P, P, P]),
+    "pld_auto_canny_u8": (I32, [P, I32, I32, I32, F64, F64, P, P, P, P, P]),
+    "pld_chamfer_dt3": (I32, [P, I32, I32, I32, F32, P, P]),
+    "pld_depth_edge_metric": (I32, [P, P, I32, I32, I32, P, P]),
     "pld_graph_begin": (I32, [P]),
     "pld_graph_end": (I32, [P, C.POINTER(P)]),
     "pld_graph_launch": (I32, [P, P]),
@@ -149,7 +157,8 @@ _NON_STATUS = {"pld_last_error", "pld_version", "pld_pgemm_ok", "pld_conv_num_ti
                "pld_sampler_compact_workspace_size", "pld_upconv_wgrad_workspace_size",
                "pld_upconv_bwd_workspace_size", "pld_se_bwd_bn_full_workspace_size",
                "pld_dwconv_dgrad_bn_bwd_workspace_size",
-               "pld_filter_refresh_plan"}
+               "pld_filter_refresh_plan",
+               "pld_minmax_u8_workspace_size", "pld_canny_workspace_size"}
 
 
 def declared_symbols(header=HEADER):

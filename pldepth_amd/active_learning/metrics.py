@@ -7,6 +7,8 @@ Same names, arguments and results as the reference:
   * ``calcDCG(rel_list)``                                      metrics.py:83-89
   * ``calc_d(op, gt, imsize=(224, 224), list_size=200)``      metrics.py:92-109
   * ``dcg_metric(model, test_im, test_gt, list_size=200)``    metrics.py:112-120
+  * ``depth_edge_metric(op, gt, imsize=(224, 224))``          metrics.py:123-144
+  * ``calc_depth_metrics(model, test_im, test_gt)``           metrics.py:147-156
 The random pixel pairs / lists are drawn on the host with the reference's exact numpy calls
 (``np.random.seed(10)`` / ``np.random.seed(69)`` + ``np.random.choice(..., replace=False)``, which
 also leave the global numpy RNG in the same state); the comparisons, min-max normalisation,
@@ -14,8 +16,14 @@ sorting and DCG sums run in ``pld_ordinal_error`` / ``pld_dcg_ratio``. Reference
 ``dcg_metric`` calls ``calc_d`` without ``imsize``, so lists are drawn from the first 224*224
 pixels whatever the image size.
 
-The edge metrics (``depth_edge_metric``, ``calc_depth_metrics``, Hausdorff helpers) need OpenCV's
-Canny / distance transform and are not part of this build.
+The edge metrics run one launch sequence per batch of images: ``pld_minmax_u8`` (8-bit maps),
+``pld_auto_canny_u8`` (median thresholds, Canny) and ``pld_depth_edge_metric`` (chamfer distance
+sums). OpenCV is not available to this build, so the 8-bit normalisation, Canny and the distance
+transform are restatements of its algorithms (unpinned, like ``calc_d``'s normalisation); the
+reference's own part (thresholds, the ``> 10`` cut, sums and division) is pinned by
+``tests/golden/edge_golden.npz``. Reference quirks kept: the distance transform is taken of the
+edge map itself (distance from an edge pixel to the nearest non-edge pixel), and a map without
+edges gives nan. The Hausdorff helpers (cKDTree tie order) are not part of this build.
 """
 import numpy as np
 import torch
@@ -120,11 +128,42 @@ def dcg_metric(model, test_im, test_gt, list_size=200):
     return float(np.mean(np.concatenate(out))) if out else float("nan")
 
 
+def _maps(a):
+    """One map as [H, W] or [H, W, 1], or a batch as [n, H, W] or [n, H, W, 1] -> [n, H, W]
+    float32 device maps."""
+    t = _dev(a)
+    if t.dim() == 3 and t.shape[-1] == 1:
+        t = t[..., 0]
+    elif t.dim() == 4:
+        t = t.reshape(t.shape[:3])
+    return (t[None] if t.dim() == 2 else t).contiguous()
+
+
+def _edge_metric_batch(p, g):
+    """p, g: [n, H, W] float32 device maps -> [n, 2] float64 (boundary, completeness)."""
+    e_op, _ = K.auto_canny(K.minmax_u8(p))
+    e_gt, _ = K.auto_canny(K.minmax_u8(g))
+    return K.depth_edge_metric(e_op, e_gt)
+
+
 def depth_edge_metric(op, gt, imsize=(224, 224)):
-    raise NotImplementedError("depth_edge_metric needs OpenCV Canny/distanceTransform "
-                              "(not part of this build; SURVEY §2 eval metrics)")
+    """(depth_boundary_error, completeness_error): both maps min-max scaled to 8 bit, their
+    auto_canny edges, and the mean over one map's edge pixels of the other edge map's chamfer
+    distance transform (values above 10 zeroed). `imsize` is unused, as in the reference; a map
+    without edges gives nan."""
+    d = _edge_metric_batch(_maps(op), _maps(gt))[0].cpu().numpy()
+    return float(d[0]), float(d[1])
 
 
 def calc_depth_metrics(model, test_im, test_gt):
-    raise NotImplementedError("calc_depth_metrics needs OpenCV Canny/distanceTransform "
-                              "(not part of this build; SURVEY §2 eval metrics)")
+    """Mean depth_edge_metric of the model's predictions over a test set (a plain mean: one nan
+    makes the mean nan)."""
+    out = []
+    for i, k, pred in _predict_batches(model, test_im):
+        g = _maps(np.asarray(test_gt[i:i + k]) if not isinstance(test_gt, torch.Tensor)
+                  else test_gt[i:i + k])
+        out.append(_edge_metric_batch(pred.reshape(g.shape).contiguous(), g).cpu().numpy())
+    if not out:
+        return float("nan"), float("nan")
+    d = np.concatenate(out)
+    return float(np.mean(d[:, 0])), float(np.mean(d[:, 1]))

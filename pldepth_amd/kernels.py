@@ -1009,6 +1009,70 @@ def dcg_ratio(pred, gt, ids):
     return out
 
 
+# ---- depth-edge metrics (pld_minmax_u8 / pld_*canny_u8 / pld_chamfer_dt3 / pld_depth_edge_metric)
+EDGE_MAX_DIM = 512  # PLD_EDGE_MAX_DIM: largest map side the Canny entry points take
+
+
+def _u8_maps(t):
+    assert t.dtype == torch.uint8 and t.dim() == 3, (t.dtype, tuple(t.shape))
+    return t.shape
+
+
+def minmax_u8(x):
+    """x: [n, ...] float32 device tensor -> uint8 tensor of the same shape, each image min-max
+    scaled to 0..255 (cv2.normalize NORM_MINMAX + astype(uint8))."""
+    n, hw = x.shape[0], x[0].numel()
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    ws = workspace(lib().pld_minmax_u8_workspace_size(n), "minmax_u8")
+    lib().pld_minmax_u8(ptr(_f32(x)), n, hw, ptr(out), ptr(ws), stream())
+    return out
+
+
+def canny(img, lo, hi, sweeps=None):
+    """img: [n, h, w] uint8 device tensor -> [n, h, w] uint8 edge maps (0 / 255) of
+    cv2.Canny(img, lo, hi). sweeps: optional [n] int32 device tensor, receives the number of
+    hysteresis passes per image."""
+    n, h, w = _u8_maps(img)
+    out = torch.empty_like(img)
+    ws = workspace(lib().pld_canny_workspace_size(n, h, w), "canny")
+    lib().pld_canny_u8(ptr(img), n, h, w, int(lo), int(hi), ptr(out), ptr(sweeps), ptr(ws),
+                       stream())
+    return out
+
+
+def auto_canny(img, sigma=1.8, sweeps=None):
+    """img: [n, h, w] uint8 device tensor -> (edges [n, h, w] uint8, thresholds [n, 2] int32) of
+    the reference's auto_canny(img, sigma): Canny between int(max(0, (1 - sigma) * median)) and
+    int(min(255, (1 + sigma) * median)), per image."""
+    n, h, w = _u8_maps(img)
+    out = torch.empty_like(img)
+    thr = torch.empty((n, 2), dtype=torch.int32, device=img.device)
+    ws = workspace(lib().pld_canny_workspace_size(n, h, w), "canny")
+    lib().pld_auto_canny_u8(ptr(img), n, h, w, 1.0 - sigma, 1.0 + sigma, ptr(thr), ptr(out),
+                            ptr(sweeps), ptr(ws), stream())
+    return out, thr
+
+
+def chamfer_dt3(mask, max_dist=10.0):
+    """mask: [n, h, w] uint8 device tensor -> [n, h, w] float32: at non-zero pixels the 3x3
+    chamfer distance to the nearest zero pixel (cv2.distanceTransform DIST_L2, 3), 0 where it
+    exceeds max_dist; 0 at zero pixels."""
+    n, h, w = _u8_maps(mask)
+    out = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
+    lib().pld_chamfer_dt3(ptr(mask), n, h, w, float(max_dist), ptr(out), stream())
+    return out
+
+
+def depth_edge_metric(edges_op, edges_gt):
+    """edges_op, edges_gt: [n, h, w] uint8 edge maps -> [n, 2] float64
+    (depth_boundary_error, completeness_error) per image."""
+    n, h, w = _u8_maps(edges_op)
+    assert tuple(edges_gt.shape) == (n, h, w) and edges_gt.dtype == torch.uint8
+    out = torch.empty((n, 2), dtype=torch.float64, device=edges_op.device)
+    lib().pld_depth_edge_metric(ptr(edges_op), ptr(edges_gt), n, h, w, ptr(out), stream())
+    return out
+
+
 # ---- HR-WSI resizing (pld_resize_bilinear / pld_resize_nearest) ----
 def resize(x, oh, ow, method="bilinear", out=None):
     """x: [n, h, w, c] float32 device tensor -> [n, oh, ow, c] (tf.image.resize, TF2 semantics)."""

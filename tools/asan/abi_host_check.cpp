@@ -128,6 +128,27 @@ int main() {
   EXPECT(pld_filter_split(nullptr, 4, 12, nullptr, nullptr) != 0);
   EXPECT(std::strlen(pld_last_error()) > 0);
 
+  // depth-edge metrics: workspace planners, null checks, and the size limits, which are
+  // refused before the pointers are looked at
+  EXPECT(pld_minmax_u8_workspace_size(0) == 0 && pld_minmax_u8_workspace_size(8) > 0);
+  EXPECT(pld_canny_workspace_size(1, 0, 8) == 0);
+  EXPECT(pld_canny_workspace_size(2, 448, 448) == (2 * 256 + 2 * 2 * 448 * 14) * 4u);
+  EXPECT(pld_minmax_u8(nullptr, 1, 64, nullptr, nullptr, nullptr) == PLD_ERR_ARG);
+  EXPECT(pld_canny_u8(nullptr, 1, 8, 8, 0, 255, nullptr, nullptr, nullptr, nullptr) ==
+         PLD_ERR_ARG);
+  EXPECT(pld_depth_edge_metric(nullptr, nullptr, 1, 8, 8, nullptr, nullptr) == PLD_ERR_ARG);
+  {
+    uint8_t img[4] = {0}, out[4] = {0}, ws[4] = {0};
+    int32_t thr[2] = {0};
+    float dt[4] = {0};
+    EXPECT(pld_canny_u8(img, 1, PLD_EDGE_MAX_DIM + 1, 8, 0, 255, out, nullptr, ws, nullptr) ==
+           PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_auto_canny_u8(img, 1, 8, PLD_EDGE_MAX_DIM + 1, -0.8, 2.8, thr, out, nullptr, ws,
+                             nullptr) == PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_chamfer_dt3(img, 1, 2, 2, 11.f, dt, nullptr) == PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_chamfer_dt3(img, 1, 2, 2, -1.f, dt, nullptr) == PLD_ERR_ARG);
+  }
+
   if (failures) {
     std::fprintf(stderr, "%d failures\n", failures);
     return 1;
