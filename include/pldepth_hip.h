@@ -495,6 +495,38 @@ int pld_se_bwd_bn_full(const float* dy, const float* x, const float* mean, const
                        const float* gate, float* addn, float* dx, int dx_accumulate,
                        float* dgamma, float* dbeta, int param_accumulate, void* ws,
                        size_t ws_bytes, void* stream);
+/* pld_se_bwd_bn_full stopped before its elementwise pass: addn, dgamma / dbeta and the block
+ * BN's k12 = [mean dz | mean dz xhat] (2c floats, 16-byte aligned, the caller's buffer) for a
+ * consumer that applies the BN backward as it reads (pld_dwconv_dgrad_se_bn). No dx is
+ * written. Workspace: pld_se_bwd_bn_full_workspace_size. */
+int pld_se_bwd_bn_coeffs(const float* dy, const float* x, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, int act, int n, int hw, int c,
+                         int cse, const float* w1, const float* w2, const float* z1,
+                         const float* gate, float* addn, float* dgamma, float* dbeta,
+                         int param_accumulate, float* k12, void* ws, size_t ws_bytes,
+                         void* stream);
+/* The stride-1 depthwise input gradient of an MBConv block taken straight from the gradient dy
+ * of the SE output (pl_hourglass.py:52-57 via Keras EfficientNet block: dwconv -> bn -> swish ->
+ * SE): the block BN's backward of (x = the depthwise output, dy; gate, addn [n][c]; k12 from
+ * pld_se_bwd_bn_coeffs) is applied to the window as it is staged, bit for bit the dx that
+ * pld_se_bwd_bn_full writes, which is never materialised. dact (=|+= by accumulate) is what
+ * pld_dwconv_dgrad gives from that dx. ex != NULL: also the backward reductions of the BN +
+ * swish that produced the depthwise input (the expand BN; ex its input), gathered from dact as
+ * it is stored: edgamma / edbeta (param_accumulate) and ek12 (2c floats) as
+ * pld_dwconv_dgrad_bn_bwd leaves them, and, when edx != NULL, edx = that BN's input gradient as
+ * pld_bn_bwd writes it; ws from pld_dwconv_dgrad_se_bn_workspace_size (unused without ex). LDS-tiled kernel only (k 3 / 5, c % 16 == 0, 16-byte aligned tensors, act and
+ * eact swish): PLD_ERR_UNSUPPORTED otherwise, and the caller runs pld_se_bwd_bn_full +
+ * pld_dwconv_dgrad. */
+size_t pld_dwconv_dgrad_se_bn_workspace_size(int n, int h, int w, int c);
+int pld_dwconv_dgrad_se_bn(const float* dy, const float* x, int n, int h, int w, int c,
+                           const float* wdw, int k, int pad_t, int pad_l, int oh, int ow,
+                           const float* mean, const float* invstd, const float* gamma,
+                           const float* beta, const float* k12, int act, const float* gate,
+                           const float* addn, float* dact, int accumulate, const float* ex,
+                           const float* emean, const float* einvstd, const float* egamma,
+                           const float* ebeta, int eact, float* edgamma, float* edbeta,
+                           int param_accumulate, float* ek12, float* edx, void* ws,
+                           size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Ranking sampler (pldepth/data/sampling.py), split into draws and a deterministic part.

@@ -122,6 +122,12 @@ _SIGS = {
     "pld_se_bwd_bn_full_workspace_size": (SZ, [I32, I32, I32, I32]),
     "pld_se_bwd_bn_full": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, I32,
                                  P, P, I32, P, SZ, P]),
+    "pld_se_bwd_bn_coeffs": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, P,
+                                   I32, P, P, SZ, P]),
+    "pld_dwconv_dgrad_se_bn_workspace_size": (SZ, [I32, I32, I32, I32]),
+    "pld_dwconv_dgrad_se_bn": (I32, [P, P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, P, P, P,
+                                     P, P, I32, P, P, P, I32, P, P, P, P, P, I32, P, P, I32, P, P,
+                                     P, SZ, P]),
     "pld_sampler_workspace_size": (SZ, [I32, I32, I32, I32, I32, I32]),
     "pld_sampler_compact": (I32, [P, I32, I32, I32, P, P, P, P, P, P]),
     "pld_sampler_compact_workspace_size": (SZ, [I32, I32, I32]),
@@ -157,6 +163,7 @@ _NON_STATUS = {"pld_last_error", "pld_version", "pld_pgemm_ok", "pld_conv_num_ti
                "pld_sampler_compact_workspace_size", "pld_upconv_wgrad_workspace_size",
                "pld_upconv_bwd_workspace_size", "pld_se_bwd_bn_full_workspace_size",
                "pld_dwconv_dgrad_bn_bwd_workspace_size",
+               "pld_dwconv_dgrad_se_bn_workspace_size",
                "pld_filter_refresh_plan",
                "pld_minmax_u8_workspace_size", "pld_canny_workspace_size"}
 

@@ -175,9 +175,9 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(RedParams p) {
         float dzv[VW];
 #pragma unroll
         for (int u = 0; u < VW; ++u) {
-          const float xh = (xv[u] - mean[u]) * inv[u];
-          const float z = (xh * gam[u] + bet[u]) + rv[u];
-          const float dz = (dv[u] * g[u] + a[u]) * act_grad(act_id, z);
+          float xh;
+          const float dz = bn_bwd_dz(act_id, xv[u], dv[u], g[u], a[u], rv[u], mean[u], inv[u],
+                                     gam[u], bet[u], xh);
           dzv[u] = dz;
           s0[u] += (double)dz;
           s1[u] += (double)dz * (double)xh;
@@ -473,11 +473,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BwdApplyParams p) {
     float o[VW], dzs[VW];
 #pragma unroll
     for (int u = 0; u < VW; ++u) {
-      const float xh = (xv[u] - mu[u]) * is[u];
-      const float z = (xh * ga[u] + be[u]) + rv[u];
-      const float dz = (dv[u] * g[u] + a[u]) * act_grad(act_id, z);
+      float xh;
+      const float dz = bn_bwd_dz(act_id, xv[u], dv[u], g[u], a[u], rv[u], mu[u], is[u], ga[u],
+                                 be[u], xh);
       dzs[u] = dz;
-      o[u] = (is[u] * ga[u]) * (dz - k1[u] - xh * k2[u]);
+      o[u] = bn_bwd_dx(dz, xh, is[u], ga[u], k1[u], k2[u]);
     }
     if (p.dres) {
 #pragma unroll

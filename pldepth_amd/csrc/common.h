@@ -82,6 +82,27 @@ __device__ __forceinline__ float act_grad(int act, float z) {
   }
 }
 
+// ---- training-mode BN (+ residual) (+ activation) backward at one element ----
+// dz = d(activation input) of y = act(bn(x) + res) for the incoming gradient dy * gate + addn
+// (an SE block's gate and squeeze term; 1 and 0 without one); xh = the normalised x. Then the BN
+// input gradient from dz and the channel's k1 = mean(dz), k2 = mean(dz xh). One definition for
+// every kernel that evaluates them (bn.hip's reduction and apply passes, dwtile.hip's dgrad
+// prologue), so that a consumer that applies the backward on the fly stages the very values
+// the apply pass would have written.
+__device__ __forceinline__ float bn_bwd_dz(int act, float x, float dy, float gate, float addn,
+                                           float res, float mu, float is, float ga, float be,
+                                           float& xh) {
+  xh = (x - mu) * is;
+  const float z = (xh * ga + be) + res;
+  // rounded on its own: where dz has no other use the product would fuse into the dz - k1 of
+  // bn_bwd_dx, and one caller's dx would differ from another's in the last bit
+  return mul_rn(dy * gate + addn, act_grad(act, z));
+}
+__device__ __forceinline__ float bn_bwd_dx(float dz, float xh, float is, float ga, float k1,
+                                           float k2) {
+  return (is * ga) * (dz - k1 - xh * k2);
+}
+
 // ---- fast unsigned division by a runtime-constant divisor (host-built magic numbers) ----
 struct FastDiv {
   uint32_t d, m, s;

@@ -722,7 +722,8 @@ extern "C" int pld__dw_tiled_ok(int k, int s, int c);
 extern "C" int pld__dw_tiled_parts(int n, int oh, int ow, int s, int c);
 extern "C" int pld__dw_dgrad_tiled(const float* dy, int n, int h, int w, int c, const float* wdw,
                                    int k, int pad_t, int pad_l, int oh, int ow, float* dx,
-                                   int accumulate, hipStream_t st);
+                                   int accumulate, const float* const* pro,
+                                   const float* const* epi, double* part, hipStream_t st);
 extern "C" int pld__dw_fwd_tiled(const float* x, int n, int h, int w, int c, const float* wdw,
                                  int k, int s, int pad_t, int pad_l, int oh, int ow,
                                  const float* mean, const float* invstd, const float* gamma,
@@ -852,7 +853,8 @@ static int dw_dgrad_impl(const float* dy, int n, int h, int w, int c, const floa
     // LDS-tiled (each dy element read once per workgroup instead of once per overlapping
     // register window: 2-3.5x the dy bytes from HBM at 14^2-28^2); same sums bit for bit
     if (grid_out) *grid_out = 0;
-    return pld__dw_dgrad_tiled(dy, n, h, w, c, wdw, k, pad_t, pad_l, oh, ow, dx, accumulate, st);
+    return pld__dw_dgrad_tiled(dy, n, h, w, c, wdw, k, pad_t, pad_l, oh, ow, dx, accumulate,
+                               nullptr, nullptr, nullptr, st);
   }
   if (s == 1) {
     constexpr int T = 4, R = 4;
@@ -900,7 +902,18 @@ extern "C" size_t pld_dwconv_dgrad_bn_bwd_workspace_size(int n, int h, int w, in
   if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 4 || (s != 1 && s != 2)) return 0;
   const long total = s == 1 ? (long)n * ((h + 3) / 4) * ((w + 3) / 4) * (c / 4)
                             : (long)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / 4);
-  return sizeof(double) * 2 * (size_t)c * dgrad_grid(total, c / 4, true);
+  const size_t regwin = sizeof(double) * 2 * (size_t)c * dgrad_grid(total, c / 4, true);
+  if (s != 1 || !pld__dw_tiled_ok(3, 1, c)) return regwin;
+  return std::max(regwin, sizeof(double) * 2 * (size_t)c * pld__dw_tiled_parts(n, h, w, 1, c));
+}
+
+// stride 1 on the LDS-tiled kernel (its EPI stage) where that kernel takes the layer
+static bool dw_dgrad_tiled_ok(const float* dy, int n, int h, int w, int c, const float* wdw, int k,
+                              int s, int pad_t, int pad_l, int oh, int ow, const float* dx) {
+  return dy && wdw && dx && n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && s == 1 &&
+         pld__dw_tiled_ok(k, 1, c) && pad_t >= 0 && pad_l >= 0 && pad_t < k && pad_l < k &&
+         (long)n * h * w * c < (1L << 31) && (long)n * oh * ow * c < (1L << 31) && aligned16(dy) &&
+         aligned16(dx) && aligned16(wdw);
 }
 
 extern "C" int pld__bn_bwd_finish(const double* part, int nparts, const float* x, const float* dy,
@@ -924,6 +937,18 @@ extern "C" int pld_dwconv_dgrad_bn_bwd(const float* dy, int n, int h, int w, int
   const size_t need = pld_dwconv_dgrad_bn_bwd_workspace_size(n, h, w, c, s);
   PLD_CHECK_ARG(need > 0 && ws_bytes >= need, "pld_dwconv_dgrad_bn_bwd: workspace %zu < %zu",
                 ws_bytes, need);
+  if (act == ACT_SWISH && dw_dgrad_tiled_ok(dy, n, h, w, c, wdw, k, s, pad_t, pad_l, oh, ow, dact)) {
+    // the tiled kernel reads dy once per workgroup; the register-window kernel below re-reads
+    // it per overlapping window
+    const float* const epi[5] = {x, mean, invstd, gamma, beta};
+    int rc = pld__dw_dgrad_tiled(dy, n, h, w, c, wdw, k, pad_t, pad_l, oh, ow, dact, accumulate,
+                                 nullptr, epi, (double*)ws, as_stream(stream));
+    if (rc) return rc;
+    return pld__bn_bwd_finish((const double*)ws, pld__dw_tiled_parts(n, h, w, 1, c), x, dact,
+                              (int64_t)n * h * w, c, mean, invstd, gamma, beta, act, nullptr,
+                              nullptr, 0, dx, dx_accumulate, dgamma, dbeta, param_accumulate, k12,
+                              as_stream(stream));
+  }
   const DwBnb b{x, mean, invstd, gamma, beta, act, (double*)ws};
   unsigned grid = 0;
   int rc = dw_dgrad_impl(dy, n, h, w, c, wdw, k, s, pad_t, pad_l, oh, ow, dact, accumulate, &b,
@@ -1038,15 +1063,16 @@ extern "C" size_t pld_se_bwd_bn_full_workspace_size(int n, int hw, int c, int cs
   return sizeof(double) * se_bn_ws_parts(n, hw, c) * 7 + 2 * sizeof(float) * (size_t)c + 64;
 }
 
-extern "C" int pld_se_bwd_bn_full(const float* dy, const float* x, const float* mean,
-                                  const float* invstd, const float* gamma, const float* beta,
-                                  int act, int n, int hw, int c, int cse, const float* w1,
-                                  const float* w2, const float* z1, const float* gate,
-                                  float* addn, float* dx, int dx_accumulate, float* dgamma,
-                                  float* dbeta, int param_accumulate, void* ws, size_t ws_bytes,
-                                  void* stream) {
+// dx NULL: stops after the finalize (addn, dgamma, dbeta, k12), k12 then the caller's buffer
+static int se_bwd_bn_impl(const float* dy, const float* x, const float* mean,
+                          const float* invstd, const float* gamma, const float* beta,
+                          int act, int n, int hw, int c, int cse, const float* w1,
+                          const float* w2, const float* z1, const float* gate,
+                          float* addn, float* dx, int dx_accumulate, float* dgamma,
+                          float* dbeta, int param_accumulate, float* k12_out, void* ws,
+                          size_t ws_bytes, void* stream) {
   PLD_CHECK_ARG(dy && x && mean && invstd && gamma && beta && w1 && w2 && z1 && gate && addn &&
-                    dx && dgamma && dbeta && ws && n > 0 && hw > 0 && c > 0 && cse > 0,
+                    (dx || k12_out) && dgamma && dbeta && ws && n > 0 && hw > 0 && c > 0 && cse > 0,
                 "pld_se_bwd_bn_full: bad args");
   PLD_CHECK_ARG(c % 4 == 0, "pld_se_bwd_bn_full: channels must be a multiple of 4");
   PLD_CHECK_ARG((long)n * hw * c < (1L << 31), "pld_se_bwd_bn_full: tensor too large");
@@ -1058,7 +1084,7 @@ extern "C" int pld_se_bwd_bn_full(const float* dy, const float* x, const float* 
   double* part = (double*)ws;
   double* part4 = part + np;
   double* bnpart = part4 + 4 * np;
-  float* k12 = (float*)(bnpart + 2 * np);
+  float* k12 = k12_out ? k12_out : (float*)(bnpart + 2 * np);
   const SePro pr{mean, invstd, gamma, beta, act};
   dim3 g1(n * rs, cdiv(c / 4, 256));
   img_chan_sum_kernel<true, true><<<g1, 256, 0, st>>>(x, dy, hw, c, rs, pr, part, part4);
@@ -1071,4 +1097,77 @@ extern "C" int pld_se_bwd_bn_full(const float* dy, const float* x, const float* 
   return pld__bn_bwd_finish(bnpart, n * rs, x, dy, (int64_t)n * hw, c, mean, invstd, gamma, beta,
                             act, gate, addn, hw, dx, dx_accumulate, dgamma, dbeta,
                             param_accumulate, k12, st);
+}
+
+extern "C" int pld_se_bwd_bn_full(const float* dy, const float* x, const float* mean,
+                                  const float* invstd, const float* gamma, const float* beta,
+                                  int act, int n, int hw, int c, int cse, const float* w1,
+                                  const float* w2, const float* z1, const float* gate,
+                                  float* addn, float* dx, int dx_accumulate, float* dgamma,
+                                  float* dbeta, int param_accumulate, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  PLD_CHECK_ARG(dx, "pld_se_bwd_bn_full: dx is NULL");
+  return se_bwd_bn_impl(dy, x, mean, invstd, gamma, beta, act, n, hw, c, cse, w1, w2, z1, gate,
+                        addn, dx, dx_accumulate, dgamma, dbeta, param_accumulate, nullptr, ws,
+                        ws_bytes, stream);
+}
+
+extern "C" int pld_se_bwd_bn_coeffs(const float* dy, const float* x, const float* mean,
+                                    const float* invstd, const float* gamma, const float* beta,
+                                    int act, int n, int hw, int c, int cse, const float* w1,
+                                    const float* w2, const float* z1, const float* gate,
+                                    float* addn, float* dgamma, float* dbeta,
+                                    int param_accumulate, float* k12, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  PLD_CHECK_ARG(k12, "pld_se_bwd_bn_coeffs: k12 is NULL");
+  return se_bwd_bn_impl(dy, x, mean, invstd, gamma, beta, act, n, hw, c, cse, w1, w2, z1, gate,
+                        addn, nullptr, 0, dgamma, dbeta, param_accumulate, k12, ws, ws_bytes,
+                        stream);
+}
+
+extern "C" size_t pld_dwconv_dgrad_se_bn_workspace_size(int n, int h, int w, int c) {
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || !pld__dw_tiled_ok(3, 1, c)) return 0;
+  return sizeof(double) * 2 * (size_t)c * pld__dw_tiled_parts(n, h, w, 1, c);
+}
+
+extern "C" int pld_dwconv_dgrad_se_bn(const float* dy, const float* x, int n, int h, int w, int c,
+                                      const float* wdw, int k, int pad_t, int pad_l, int oh,
+                                      int ow, const float* mean, const float* invstd,
+                                      const float* gamma, const float* beta, const float* k12,
+                                      int act, const float* gate, const float* addn, float* dact,
+                                      int accumulate, const float* ex, const float* emean,
+                                      const float* einvstd, const float* egamma,
+                                      const float* ebeta, int eact, float* edgamma, float* edbeta,
+                                      int param_accumulate, float* ek12, float* edx,
+                                      void* ws, size_t ws_bytes, void* stream) {
+  PLD_CHECK_ARG(x && mean && invstd && gamma && beta && k12 && gate && addn,
+                "pld_dwconv_dgrad_se_bn: bad block BN / SE args");
+  PLD_CHECK_ARG(aligned16(x) && aligned16(mean) && aligned16(invstd) && aligned16(gamma) &&
+                    aligned16(beta) && aligned16(k12) && aligned16(gate) && aligned16(addn),
+                "pld_dwconv_dgrad_se_bn: block BN / SE tensors must be 16-byte aligned");
+  if (act != ACT_SWISH || (ex && eact != ACT_SWISH) ||
+      !dw_dgrad_tiled_ok(dy, n, h, w, c, wdw, k, 1, pad_t, pad_l, oh, ow, dact)) {
+    set_error("pld_dwconv_dgrad_se_bn: needs the LDS-tiled stride-1 dgrad (k 3 / 5, C %% 16 == 0, "
+              "16-byte aligned tensors) and swish BNs");
+    return PLD_ERR_UNSUPPORTED;
+  }
+  const float* const pro[8] = {x, mean, invstd, gamma, beta, k12, gate, addn};
+  hipStream_t st = as_stream(stream);
+  if (!ex)
+    return pld__dw_dgrad_tiled(dy, n, h, w, c, wdw, k, pad_t, pad_l, oh, ow, dact, accumulate,
+                               pro, nullptr, nullptr, st);
+  PLD_CHECK_ARG(emean && einvstd && egamma && ebeta && ek12 && ws && aligned16(ex) &&
+                    aligned16(emean) && aligned16(einvstd) && aligned16(egamma) &&
+                    aligned16(ebeta),
+                "pld_dwconv_dgrad_se_bn: bad expand BN args (16-byte aligned)");
+  const size_t need = pld_dwconv_dgrad_se_bn_workspace_size(n, h, w, c);
+  PLD_CHECK_ARG(need > 0 && ws_bytes >= need, "pld_dwconv_dgrad_se_bn: workspace %zu < %zu",
+                ws_bytes, need);
+  const float* const epi[5] = {ex, emean, einvstd, egamma, ebeta};
+  int rc = pld__dw_dgrad_tiled(dy, n, h, w, c, wdw, k, pad_t, pad_l, oh, ow, dact, accumulate, pro,
+                               epi, (double*)ws, st);
+  if (rc) return rc;
+  return pld__bn_bwd_finish((const double*)ws, pld__dw_tiled_parts(n, h, w, 1, c), ex, dact,
+                            (int64_t)n * h * w, c, emean, einvstd, egamma, ebeta, eact, nullptr,
+                            nullptr, 0, edx, 0, edgamma, edbeta, param_accumulate, ek12, st);
 }

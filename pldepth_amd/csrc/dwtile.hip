@@ -35,6 +35,18 @@ struct Geo {
   int tiles_x, tiles_y;
   int per;              // tiles per workgroup (a contiguous run of its channel group's tiles)
   int accum;            // DG: y += result
+  // DG with PRO: x is the gradient of an SE block's output and the staged value the block BN's
+  // backward of it (mean / invstd / gamma / beta above are that BN's vectors, ACT its activation)
+  const float* x2;      // that BN's input, shaped like x
+  const float* k12;     // its [k1 | k2] (bnbwd_finalize_kernel)
+  const float* gate;    // [n][c] SE gate
+  const float* addn;    // [n][c] SE squeeze term
+  // DG with EPI: the backward sums of the BN + swish that produced the depthwise input
+  const float* ex;      // that BN's input, shaped like y
+  const float* emean;
+  const float* einvstd;
+  const float* egamma;
+  const float* ebeta;
 };
 
 __device__ __forceinline__ float4 fma4(float4 acc, float4 v, float4 f) {
@@ -74,9 +86,15 @@ static void tile_plan(int n, int oh, int ow, int s, int c, int& per, int& nbx) {
 // DG (stride 1): the input gradient of a stride-1 depthwise conv as this correlation of dy with
 // the flipped filter, window pads K - 1 - pad; the taps of every output summed in ascending
 // (ty, tx) order of the unflipped filter, as dwconv_dgrad_s1_kernel (dwse.hip) sums them, so the
-// two paths agree bit for bit (the BN-fused dgrad epilogue stays on that kernel).
-template <int K, int S, int CQ, int ACT, bool DG = false>  // ACT < 0: no prologue
-__global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
+// two paths agree bit for bit.
+// PRO: the window is staged as the BN + swish backward (bn_bwd_apply_kernel's value, from
+// common.h's bn_bwd_dz / bn_bwd_dx) of (x, x2) instead of x itself: the MBConv block BN's input
+// gradient is consumed here and never written. EPI: the sums of the expand BN's backward
+// (dz = result * swish'(bn(ex)), dz xhat) gathered from the stored result in the statistics
+// accumulators. The per-quad BN vectors of both stages live in LDS and are read in the staging /
+// store phases only, so that they hold no registers across the FMAs.
+template <int K, int S, int CQ, int ACT, bool DG = false, bool PRO = false, bool EPI = false>
+__global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {  // ACT < 0: no prologue
   constexpr int TO = tile_cols(S);                // output tile width
   constexpr int TOH = tile_rows(S, CQ);           // output tile height
   constexpr int TI = (TO - 1) * S + K;            // input window width
@@ -89,9 +107,13 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
   constexpr int NE = TIR * TI * CQ;               // window float4s
   constexpr int NL = (NE + 255) / 256;
   static_assert(256 % CQ == 0, "a thread's staged channel quad is tid % CQ on every load");
-  static_assert(!DG || (S == 1 && ACT < 0), "the dgrad form is stride 1 without a prologue");
+  static_assert(!DG || S == 1, "the dgrad form is stride 1");
+  static_assert(DG ? (ACT >= 0) == PRO : !(PRO || EPI), "the BN backward stages belong to the dgrad");
+  constexpr bool FPRO = ACT >= 0 && !DG;          // the forward's act(bn(x)) prologue
   extern __shared__ __attribute__((aligned(16))) float4 tile[];  // [TIR][COLS][CQ], [K K][CQ]
   float4* ftile = tile + TIR * COLS * CQ;
+  float4* ptile = ftile + (K == 5 ? K * K * CQ : 0);  // PRO: [mean invstd gamma beta k1 k2][CQ]
+  float4* etile = ptile + (PRO ? 6 * CQ : 0);         // EPI: [mean invstd gamma beta][CQ]
   const int tid = threadIdx.x;
   const int cb = blockIdx.y * CQ * 4;             // first channel of the group
   const int ntx = g.tiles_x, nt = g.tiles_x * g.tiles_y;
@@ -101,7 +123,7 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
   const bool qok = cb + 4 * q < g.c;  // the last group of a C % 32 == 16 layer is half full
   const float* fq = g.w + (qok ? cb + 4 * q : 0);  // this thread's filter quad: tap t at fq + t C
   float4 mu, is, ga, be;
-  if (ACT >= 0 && qok) {
+  if (FPRO && qok) {
     mu = *reinterpret_cast<const float4*>(g.mean + cb + 4 * q);
     is = *reinterpret_cast<const float4*>(g.invstd + cb + 4 * q);
     ga = *reinterpret_cast<const float4*>(g.gamma + cb + 4 * q);
@@ -122,6 +144,23 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
                                    : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
+  if constexpr (PRO || EPI) {
+    const int qq = tid % CQ, j = tid / CQ;  // vector j of quad qq
+    const bool in = cb + 4 * qq < g.c;
+    if (PRO && j < 6) {
+      const float* p = j == 0 ? g.mean : j == 1 ? g.invstd : j == 2 ? g.gamma : j == 3 ? g.beta
+                     : j == 4 ? g.k12 : g.k12 + g.c;
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in) t = *reinterpret_cast<const float4*>(p + cb + 4 * qq);
+      ptile[tid] = t;
+    }
+    if (EPI && j < 4) {
+      const float* p = j == 0 ? g.emean : j == 1 ? g.einvstd : j == 2 ? g.egamma : g.ebeta;
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in) t = *reinterpret_cast<const float4*>(p + cb + 4 * qq);
+      etile[tid] = t;
+    }
+  }
   auto origin = [&](int sp, int& img, int& oy0, int& ox0) {
     img = sp / nt;
     const int rr = sp - img * nt;
@@ -129,6 +168,7 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
     ox0 = (rr % ntx) * TO;
   };
   float4 v[NL];
+  float4 v2[PRO ? NL : 1], gt, ad;  // PRO: the x2 window and the image's gate / addn quads
   auto load_window = [&](int sp) {
     int img, oy0, ox0;
     origin(sp, img, oy0, ox0);
@@ -143,6 +183,16 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
       const bool ok = e < NE && (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.wd && qok;
       v[i] = ok ? *reinterpret_cast<const float4*>(xb + ((long)iy * g.wd + ix) * g.c + 4 * q)
                 : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (PRO)
+        v2[i] = ok ? *reinterpret_cast<const float4*>(g.x2 + (long)img * g.h * g.wd * g.c + cb +
+                                                      ((long)iy * g.wd + ix) * g.c + 4 * q)
+                   : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if constexpr (PRO) {  // a tile lies in one image; a workgroup's run of tiles crosses images
+      gt = qok ? *reinterpret_cast<const float4*>(g.gate + (long)img * g.c + cb + 4 * q)
+               : make_float4(0.f, 0.f, 0.f, 0.f);
+      ad = qok ? *reinterpret_cast<const float4*>(g.addn + (long)img * g.c + cb + 4 * q)
+               : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
   const int oc = (tid / CQ) % TO, rg = tid / (CQ * TO);
@@ -154,6 +204,11 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
     const int iy0 = oy0 * S - g.pt, ix0 = ox0 * S - g.pl;
     __syncthreads();  // the previous tile's window is no longer read
     // ---- the prologue and the LDS stores of this tile's window ----
+    float4 k1, k2;
+    if constexpr (PRO) {
+      mu = ptile[q]; is = ptile[CQ + q]; ga = ptile[2 * CQ + q]; be = ptile[3 * CQ + q];
+      k1 = ptile[4 * CQ + q]; k2 = ptile[5 * CQ + q];
+    }
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int e = tid + 256 * i;
@@ -162,7 +217,23 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
       const int wy = px / TI, wx = px - wy * TI;
       const int iy = iy0 + wy, ix = ix0 + wx;
       float4 a = v[i];
-      if (ACT >= 0 && (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.wd && qok) {
+      if constexpr (PRO) {
+        // outside the image (and in a half-full group's idle quads) the staged gradient is an
+        // exact zero: the BN backward of a zero is not
+        if ((unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.wd && qok) {
+          const float4 x = v2[i];
+          float xh;
+          float dz = bn_bwd_dz(ACT, x.x, a.x, gt.x, ad.x, 0.f, mu.x, is.x, ga.x, be.x, xh);
+          a.x = bn_bwd_dx(dz, xh, is.x, ga.x, k1.x, k2.x);
+          dz = bn_bwd_dz(ACT, x.y, a.y, gt.y, ad.y, 0.f, mu.y, is.y, ga.y, be.y, xh);
+          a.y = bn_bwd_dx(dz, xh, is.y, ga.y, k1.y, k2.y);
+          dz = bn_bwd_dz(ACT, x.z, a.z, gt.z, ad.z, 0.f, mu.z, is.z, ga.z, be.z, xh);
+          a.z = bn_bwd_dx(dz, xh, is.z, ga.z, k1.z, k2.z);
+          dz = bn_bwd_dz(ACT, x.w, a.w, gt.w, ad.w, 0.f, mu.w, is.w, ga.w, be.w, xh);
+          a.w = bn_bwd_dx(dz, xh, is.w, ga.w, k1.w, k2.w);
+        }
+      }
+      if (FPRO && (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.wd && qok) {
         // bn_apply's arithmetic, then the activation (TF pads the activated map with zeros)
         a = make_float4(act_fwd(ACT, ((a.x - mu.x) * is.x) * ga.x + be.x),
                         act_fwd(ACT, ((a.y - mu.y) * is.y) * ga.y + be.y),
@@ -224,17 +295,45 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
     // ---- store (+ statistics) ----
     const int ox = ox0 + oc;
     if (ox < g.ow && qok) {
+      float4 xe[EPI ? R : 1], emu, eis, ega, ebe;
+      // all R rows of ex in flight before the first is used, except where both stages leave no
+      // registers for them (k3: the 9 filter taps stay in registers)
+      constexpr bool XB = !(K == 3 && PRO);
+      if constexpr (EPI && XB) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int oy = min(oy0 + rg * R + r, g.oh - 1);  // clamped: rows past the map unused
+          xe[r] = *reinterpret_cast<const float4*>(g.ex + (((long)img * g.oh + oy) * g.ow + ox) * g.c + cb + 4 * q);
+        }
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int oy = oy0 + rg * R + r;
         if (oy >= g.oh) break;
         float4* yp = reinterpret_cast<float4*>(g.y + (((long)img * g.oh + oy) * g.ow + ox) * g.c + cb + 4 * q);
+        if constexpr (EPI && !XB)
+          xe[0] = *reinterpret_cast<const float4*>(g.ex + (((long)img * g.oh + oy) * g.ow + ox) * g.c + cb + 4 * q);
         if (DG && g.accum) {
           const float4 old = *yp;
           acc[r].x += old.x; acc[r].y += old.y; acc[r].z += old.z; acc[r].w += old.w;
         }
         *yp = acc[r];
-        if (g.stats) {
+        if constexpr (EPI) {
+          // chan_reduce_kernel's BN backward sums of (ex, the stored gradient)
+          const float a4[4] = {acc[r].x, acc[r].y, acc[r].z, acc[r].w};
+          const float4 xr = xe[XB ? r : 0];
+          emu = etile[q]; eis = etile[CQ + q]; ega = etile[2 * CQ + q]; ebe = etile[3 * CQ + q];
+          const float x4[4] = {xr.x, xr.y, xr.z, xr.w};
+          const float m4[4] = {emu.x, emu.y, emu.z, emu.w}, i4[4] = {eis.x, eis.y, eis.z, eis.w};
+          const float g4[4] = {ega.x, ega.y, ega.z, ega.w}, b4[4] = {ebe.x, ebe.y, ebe.z, ebe.w};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            float xh;
+            const float dz = bn_bwd_dz(ACT_SWISH, x4[u], a4[u], 1.f, 0.f, 0.f, m4[u], i4[u], g4[u], b4[u], xh);
+            s1[u] += (double)dz;
+            s2[u] += (double)dz * (double)xh;
+          }
+        } else if (g.stats) {
           const float a4[4] = {acc[r].x, acc[r].y, acc[r].z, acc[r].w};
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
@@ -246,7 +345,7 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
       }
     }
   }
-  if (!g.stats) return;
+  if (!EPI && !g.stats) return;
   __syncthreads();  // the window is no longer read: reuse it for the fixed-order combine
   double* red = reinterpret_cast<double*>(tile);  // [256][8]
 #pragma unroll
@@ -270,12 +369,13 @@ __global__ __launch_bounds__(256, PLD_DW_MINB) void dw_fwd_tile_kernel(Geo g) {
 }
 
 template <int K, int S, int CQ>
-static size_t lds_bytes() {
+static size_t lds_bytes(bool pro = false, bool epi = false) {
   constexpr int TO = tile_cols(S);
   constexpr int TI = (TO - 1) * S + K;
   constexpr int TIR = (tile_rows(S, CQ) - 1) * S + K;
   constexpr int COLS = S == 1 ? TI : 2 * ((TI + 1) / 2);
-  const size_t win = sizeof(float4) * (TIR * COLS * CQ + (K == 5 ? K * K * CQ : 0));
+  const size_t win = sizeof(float4) * (TIR * COLS * CQ + (K == 5 ? K * K * CQ : 0) +
+                                       (pro ? 6 * CQ : 0) + (epi ? 4 * CQ : 0));
   return std::max(win, sizeof(double) * 256 * 8);
 }
 
@@ -331,23 +431,43 @@ extern "C" int pld__dw_fwd_tiled(const float* x, int n, int h, int w, int c, con
   return check_launch("dw_fwd_tile_kernel");
 }
 
-// stride-1 input gradient through the tiled kernel (DG): dx [n][h][w][c] from dy [n][oh][ow][c]
+// stride-1 input gradient through the tiled kernel (DG): dx [n][h][w][c] from dy [n][oh][ow][c].
+// pro (or NULL): {x2, mean, invstd, gamma, beta, k12, gate, addn}, dy is then the gradient of an SE
+// block's output and the BN + swish backward of (x2, dy) is what the conv sees. epi (or NULL):
+// {ex, mean, invstd, gamma, beta}, the BN + swish backward sums of (ex, dx) go to part as
+// [c][pld__dw_tiled_parts(n, h, w, 1, c)][2].
 extern "C" int pld__dw_dgrad_tiled(const float* dy, int n, int h, int w, int c, const float* wdw,
                                    int k, int pad_t, int pad_l, int oh, int ow, float* dx,
-                                   int accumulate, hipStream_t st) {
+                                   int accumulate, const float* const* pro,
+                                   const float* const* epi, double* part, hipStream_t st) {
   dwt::Geo g{};
   g.x = dy; g.w = wdw; g.y = dx;
   g.n = n; g.h = oh; g.wd = ow; g.c = c; g.oh = h; g.ow = w;
   g.pt = k - 1 - pad_t; g.pl = k - 1 - pad_l;
   g.accum = accumulate;
+  if (pro) {
+    g.x2 = pro[0]; g.mean = pro[1]; g.invstd = pro[2]; g.gamma = pro[3]; g.beta = pro[4];
+    g.k12 = pro[5]; g.gate = pro[6]; g.addn = pro[7];
+  }
+  if (epi) {
+    g.ex = epi[0]; g.emean = epi[1]; g.einvstd = epi[2]; g.egamma = epi[3]; g.ebeta = epi[4];
+    g.stats = part;
+  }
   g.tiles_x = (int)cdiv(w, dwt::tile_cols(1));
   g.tiles_y = (int)cdiv(h, dwt::tile_rows(1, 8));
   int nbx;
   dwt::tile_plan(n, h, w, 1, c, g.per, nbx);
   dim3 grid(nbx, (int)cdiv(c, 32));
-  if (k == 3)
-    dwt::dw_fwd_tile_kernel<3, 1, 8, -1, true><<<grid, 256, dwt::lds_bytes<3, 1, 8>(), st>>>(g);
-  else
-    dwt::dw_fwd_tile_kernel<5, 1, 8, -1, true><<<grid, 256, dwt::lds_bytes<5, 1, 8>(), st>>>(g);
+#define DWT_DG(KK, A, P, E)                                                                      \
+  dwt::dw_fwd_tile_kernel<KK, 1, 8, A, true, P, E>                                               \
+      <<<grid, 256, dwt::lds_bytes<KK, 1, 8>(P, E), st>>>(g)
+#define DWT_DGK(KK)                                                                              \
+  if (pro && epi) DWT_DG(KK, ACT_SWISH, true, true);                                             \
+  else if (pro) DWT_DG(KK, ACT_SWISH, true, false);                                              \
+  else if (epi) DWT_DG(KK, -1, false, true);                                                     \
+  else DWT_DG(KK, -1, false, false);
+  if (k == 3) { DWT_DGK(3) } else { DWT_DGK(5) }
+#undef DWT_DGK
+#undef DWT_DG
   return check_launch("dw_fwd_tile_kernel(dgrad)");
 }

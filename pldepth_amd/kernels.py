@@ -911,6 +911,61 @@ def dwconv_dgrad_bn_bwd(dy, wdw, k, s, pad_t, pad_l, dact, x, bn, act, dgamma, d
                                   ptr(ws), need, stream())
 
 
+def dwconv_dgrad_se_bn(dy, x, bn, k12, gate, addn, wdw, k, pad_t, pad_l, dact, ex=None, ebn=None,
+                       edgamma=None, edbeta=None, ek12=None, edx=None, act="swish", eact="swish",
+                       accumulate=False, param_accumulate=False):
+    """The stride-1 dwconv_dgrad of an MBConv block read straight from the SE output's gradient
+    dy: the block BN's backward (x: its input, bn = (mean, invstd, gamma, beta), k12 / addn from
+    se_bwd_bn_coeffs, the SE gate) is applied as the window is staged, so the dx of
+    se_bwd_bn_full is never written. With ex / ebn (the expand BN and its input) the dgrad's
+    epilogue also gathers that BN's backward sums: edgamma, edbeta and ek12 as bn_bwd_coeffs
+    leaves them, and edx (when given) that BN's input gradient. Raises PLDError where the LDS-tiled kernel does not take the layer."""
+    n, h, w, c = dact.shape
+    _, oh, ow, _ = dy.shape
+    mean, invstd, gamma, beta = bn
+    em, ei, eg, eb = ebn if ex is not None else (None,) * 4
+    need = lib().pld_dwconv_dgrad_se_bn_workspace_size(n, h, w, c) if ex is not None else 0
+    ws = workspace(need, "dwbnb") if need else None
+    lib().pld_dwconv_dgrad_se_bn(ptr(dy), ptr(x), n, h, w, c, ptr(wdw), k, pad_t, pad_l, oh, ow,
+                                 ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(k12), ACT[act],
+                                 ptr(gate), ptr(addn), ptr(dact), int(accumulate), ptr(ex),
+                                 ptr(em), ptr(ei), ptr(eg), ptr(eb), ACT[eact], ptr(edgamma),
+                                 ptr(edbeta), int(param_accumulate), ptr(ek12), ptr(edx), ptr(ws),
+                                 need, stream())
+
+
+def dw_dgrad_fuse_ok(k, c):
+    """The layers dwconv_dgrad_se_bn / the tiled dwconv_dgrad_bn_bwd take (stride 1)."""
+    return k in (3, 5) and c % 16 == 0
+
+
+def dw_dgrad_fuse_pays(k, c, h):
+    """(pro, epi): the stages EffNetFF wires into the stride-1 depthwise dgrad of a block with
+    a k x k filter, c expanded channels and an h x h map: the block BN's backward applied on
+    load (pro), the expand BN's backward sums gathered on store (epi).
+
+    Measured (tools/dw_fuse_micro.py, MI355X, 448^2 batch 32, graph replays, median us of SE
+    backward + dgrad + expand BN reductions, spread <= 5 us; profiles/r07_dw_fuse_micro.txt):
+
+        blocks    shape            pair    pro    epi   both
+        1a        224^2 x 32  k3  278.9  219.9      -      -
+        2b        112^2 x 144 k3  413.9  376.8  386.3  345.1
+        3b        56^2 x 240  k5  203.0  185.3  185.2  163.7
+        4b 4c     28^2 x 480  k3  112.4   96.1   97.9   87.3
+        5a        28^2 x 480  k5  124.8  110.4  109.2   99.3
+        5b 5c     28^2 x 672  k5  168.0  152.7  147.9  133.4
+        6b 6c 6d  14^2 x 1152 k5   95.8   87.2   88.1   80.5
+        7a        14^2 x 1152 k3   87.9   79.3   81.2   73.6
+
+    Both stages pay at every shape, so pro is wired everywhere. epi is not: its sums reach k12 in
+    another (fixed) order, 1e-8 away, and the 15 project-BN beta gradients, which are zero
+    analytically (a shift in front of a training-mode BN) and rounding residue of 1e-5 .. 1e-3
+    beside gradients of 1e3 in practice, then move by their own size; the engine's gradients
+    stay bit for bit what the unfused pair gives. PLD_DW_SE_BN=both wires it (step 15.09 ->
+    14.80 ms against 14.91 ms with pro alone, profiles/r07_dw_fuse_step_ab.txt)."""
+    return True, False
+
+
 def se_fwd(a, w1, b1, w2, b2, pooled, z1, gate, bn=None, act="swish"):
     """bn = (mean, invstd, gamma, beta): `a` is the pre-BN tensor; the squeeze applies BN + act."""
     n, h, w, c = a.shape
@@ -953,6 +1008,21 @@ def se_bwd_bn_full(dy, x, bn, w1, w2, z1, gate, addn, dx, dgamma, dbeta, act="sw
                              h * w, c, cse, ptr(w1), ptr(w2), ptr(z1), ptr(gate), ptr(addn),
                              ptr(dx), int(dx_accumulate), ptr(dgamma), ptr(dbeta),
                              int(param_accumulate), ptr(ws), need, stream())
+
+
+def se_bwd_bn_coeffs(dy, x, bn, w1, w2, z1, gate, addn, dgamma, dbeta, k12, act="swish",
+                     param_accumulate=False):
+    """se_bwd_bn_full without its elementwise pass: addn, dgamma, dbeta and the block BN's
+    k12 [2c] for dwconv_dgrad_se_bn, which applies the backward as it reads (no dx)."""
+    n, h, w, c = x.shape
+    cse = w1.shape[-1]
+    need = lib().pld_se_bwd_bn_full_workspace_size(n, h * w, c, cse)
+    ws = workspace(need, "se_bn")
+    mu, inv, g, b = bn
+    lib().pld_se_bwd_bn_coeffs(ptr(dy), ptr(x), ptr(mu), ptr(inv), ptr(g), ptr(b), ACT[act], n,
+                               h * w, c, cse, ptr(w1), ptr(w2), ptr(z1), ptr(gate), ptr(addn),
+                               ptr(dgamma), ptr(dbeta), int(param_accumulate), ptr(k12), ptr(ws),
+                               need, stream())
 
 
 # -------------------------------------------------------------------------------- sampler

@@ -128,6 +128,11 @@ class EffNetFF:
         # dgrad (concurrent with the encoder backward, which has no weight gradients of its
         # own; +0.7 % img/s, while mode 1 costs 1.5 %: profiles/r03_overlap_ab.txt); 0 = in line
         self.overlap_wgrad = int(os.environ.get("PLD_OVERLAP_WGRAD", "2"))
+        # backward: the block BN's backward applied by the stride-1 depthwise dgrad as it stages
+        # its window ("pro") and the expand BN's backward sums gathered as it stores ("epi")
+        # (csrc/dwtile.hip). "1": per block where kernels.dw_dgrad_fuse_pays measured a gain;
+        # "0": off; "pro" / "epi" / "both": that stage on every eligible block (A/B runs)
+        self.fuse_dw_dgrad = os.environ.get("PLD_DW_SE_BN", "1")
 
     # ------------------------------------------------------------------ graph structure
     def _build_spec(self):
@@ -324,13 +329,26 @@ class EffNetFF:
                                self.act["stem_activation"], True)
         return self.act[name]
 
-    def _k12_buf(self, c):
-        """BN-backward coefficients [2c] (pgemm_bn_bwd's k12), one scratch per width."""
+    def _k12_buf(self, c, slot=0):
+        """BN-backward coefficients [2c] (pgemm_bn_bwd's k12), one scratch per width (slot 1:
+        the block BN's, alive together with the expand BN's of the same width)."""
         if not hasattr(self, "_k12"):
             self._k12 = {}
-        if c not in self._k12:
-            self._k12[c] = torch.empty(2 * c, device=self.device)
-        return self._k12[c]
+        if (c, slot) not in self._k12:
+            self._k12[(c, slot)] = torch.empty(2 * c, device=self.device)
+        return self._k12[(c, slot)]
+
+    def _dw_dgrad_fuse(self, blk):
+        """(pro, epi): the BN-backward stages the block's depthwise dgrad takes on
+        (self.fuse_dw_dgrad); stride-1 blocks the LDS-tiled kernel runs only."""
+        mode = self.fuse_dw_dgrad
+        if mode == "0" or blk["s"] != 1 or not K.dw_dgrad_fuse_ok(blk["k"], blk["cexp"]):
+            return False, False
+        if mode == "1":
+            pro, epi = K.dw_dgrad_fuse_pays(blk["k"], blk["cexp"], blk["h"])
+        else:
+            pro, epi = mode in ("pro", "both"), mode in ("epi", "both")
+        return pro, epi and blk["ex"] != 1
 
     def _gpre_buf(self, shape, slot=0):
         key = (tuple(shape), slot)
@@ -659,12 +677,19 @@ class EffNetFF:
                        gp, blk["project"].w_dg, gse)
         F = self.frozen
         bn = blk["bn"]
-        gdw = self._gpre_buf(A[n + "dw_pre"].shape)
+        bnv = (bn.mean, bn.invstd, bn.gamma, bn.beta)
+        se_w = (F[blk["se_w1"]].view(blk["cexp"], blk["cse"]),
+                F[blk["se_w2"]].view(blk["cse"], blk["cexp"]))
+        pro, epi = self._dw_dgrad_fuse(blk)
         # SE backward + the block BN's backward; the BN reductions ride on the SE squeeze sweep
-        K.se_bwd_bn_full(gse, A[n + "dw_pre"], (bn.mean, bn.invstd, bn.gamma, bn.beta),
-                         F[blk["se_w1"]].view(blk["cexp"], blk["cse"]),
-                         F[blk["se_w2"]].view(blk["cse"], blk["cexp"]), blk["z1"], blk["gate"],
-                         blk["addn"], gdw, bn.dgamma, bn.dbeta, act="swish")
+        if pro:  # its elementwise pass is the depthwise dgrad's window staging: no gdw
+            bk12 = self._k12_buf(blk["cexp"], 1)
+            K.se_bwd_bn_coeffs(gse, A[n + "dw_pre"], bnv, *se_w, blk["z1"], blk["gate"],
+                               blk["addn"], bn.dgamma, bn.dbeta, bk12, act="swish")
+        else:
+            gdw = self._gpre_buf(A[n + "dw_pre"].shape)
+            K.se_bwd_bn_full(gse, A[n + "dw_pre"], bnv, *se_w, blk["z1"], blk["gate"],
+                             blk["addn"], gdw, bn.dgamma, bn.dbeta, act="swish")
         pt, pl = blk["pad"]
         if blk["ex"] != 1:
             ge = G[n + "expand_activation"]
@@ -673,23 +698,45 @@ class EffNetFF:
             ebn = blk["expand_bn"]
             bnp = (ebn.mean, ebn.invstd, ebn.gamma, ebn.beta)
             k12 = self._k12_buf(blk["cexp"])
-            K.dwconv_dgrad(gdw, F[blk["dw"]], blk["k"], blk["s"], pt, pl, ge, accumulate=is_tap)
+            # epi: the expand BN's backward sums (dgamma, dbeta, k12) come from the dgrad's
+            # epilogue, and its elementwise pass (gpe), where no pgemm folds it in, follows
+            gpe = None
+            if not blk["fused_expand_dgrad"]:
+                gpe = self._gpre_buf(A[n + "expand_pre"].shape)
+            if pro:
+                K.dwconv_dgrad_se_bn(gse, A[n + "dw_pre"], bnv, bk12, blk["gate"], blk["addn"],
+                                     F[blk["dw"]], blk["k"], pt, pl, ge,
+                                     ex=A[n + "expand_pre"] if epi else None, ebn=bnp,
+                                     edgamma=ebn.dgamma, edbeta=ebn.dbeta, ek12=k12, edx=gpe,
+                                     accumulate=is_tap)
+            elif epi:
+                K.dwconv_dgrad_bn_bwd(gdw, F[blk["dw"]], blk["k"], 1, pt, pl, ge,
+                                      A[n + "expand_pre"], bnp, "swish", ebn.dgamma, ebn.dbeta,
+                                      k12, dx=gpe, accumulate=is_tap)
+            else:
+                K.dwconv_dgrad(gdw, F[blk["dw"]], blk["k"], blk["s"], pt, pl, ge,
+                               accumulate=is_tap)
             # residual: gx_in is gy's buffer (_alloc_activations) and already holds gy
             res = blk["residual"]
             if blk["fused_expand_dgrad"]:
-                K.bn_bwd_coeffs(A[n + "expand_pre"], ge, B * h * w, blk["cexp"], *bnp, "swish",
-                                ebn.dgamma, ebn.dbeta, k12)
+                if not epi:
+                    K.bn_bwd_coeffs(A[n + "expand_pre"], ge, B * h * w, blk["cexp"], *bnp,
+                                    "swish", ebn.dgamma, ebn.dbeta, k12)
                 K.pgemm_bn_bwd(A[n + "expand_pre"], ge, B * h * w, blk["cexp"], *bnp, "swish",
                                k12, blk["expand"].w_dg, blk["cin"], gx_in, accumulate=res)
             else:
-                gpe = self._gpre_buf(A[n + "expand_pre"].shape)
-                ebn.bwd(A[n + "expand_pre"], ge, B * h * w, "swish", gpe)
+                if not epi:
+                    ebn.bwd(A[n + "expand_pre"], ge, B * h * w, "swish", gpe)
                 K.conv2d_dgrad(K.conv_args(x_in, None, 1, 1, 1, 0, 0, h, w, blk["cexp"],
                                            math=self._em(h, w)), gpe, blk["expand"].w_dg, gx_in,
                                acc1=res)
         else:
             assert not blk["residual"]
-            K.dwconv_dgrad(gdw, F[blk["dw"]], blk["k"], blk["s"], pt, pl, gx_in)
+            if pro:
+                K.dwconv_dgrad_se_bn(gse, A[n + "dw_pre"], bnv, bk12, blk["gate"], blk["addn"],
+                                     F[blk["dw"]], blk["k"], pt, pl, gx_in)
+            else:
+                K.dwconv_dgrad(gdw, F[blk["dw"]], blk["k"], blk["s"], pt, pl, gx_in)
 
     # ------------------------------------------------------------------ optimizer
     def adam_state(self):
