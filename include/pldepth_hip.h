@@ -622,6 +622,66 @@ int pld_depth_edge_metric(const uint8_t* edges_op, const uint8_t* edges_gt, int 
                           double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Active-learning selection (pldepth/run_scripts/active_PLDepth.py:160-185):
+ * pldepth/active_learning/active_learning_method.py with the helpers it calls in metrics.py:9-57
+ * and preprocess_utils.py:16-42, each entry point for a batch of n images. u8 maps are
+ * [n][h][w] bytes. The OpenCV calls on the way (cvtColor, medianBlur, normalize, GaussianBlur)
+ * are restated; a limit that is exceeded returns PLD_ERR_UNSUPPORTED before anything is
+ * launched.
+ * ------------------------------------------------------------------------------------------ */
+#define PLD_MEDIAN_MAX_KSIZE 15
+#define PLD_TILE_MAX 32
+#define PLD_ORACLE_MAX_L 16
+/* active_learning_method.py:94 cv2.cvtColor(img, COLOR_RGB2GRAY) on float32 images of hw RGB
+ * pixels: gray = (r * 0.299f + g * 0.587f) + b * 0.114f, each product and sum rounded on its
+ * own. */
+int pld_gray_f32(const float* rgb, int n, int64_t hw, float* gray, void* stream);
+/* active_learning_method.py:96 cv2.medianBlur(img, ksize) on 8-bit maps: the median of the
+ * ksize x ksize window with the border replicated; ksize odd, 3 .. PLD_MEDIAN_MAX_KSIZE. */
+int pld_median_blur_u8(const uint8_t* img_u8, int n, int h, int w, int ksize, uint8_t* out_u8,
+                       void* stream);
+/* active_learning_method.py:103-104: with normalize != 0, cv2.normalize(x, None, 0, 255,
+ * NORM_MINMAX) as float32 (scale and shift as pld_minmax_u8, without the truncation; with
+ * normalize == 0 the map is taken as it is), then preprocess_utils.py:16-26
+ * unsharp_mask(., (5, 5), sigma, amount, threshold=0): the separable 5-tap Gaussian
+ * (exp(-d^2 / (2 sigma^2)) normalised in double, stored as fp32; BORDER_REFLECT_101; rows, then
+ * columns, taps summed from the lowest index up), (amount + 1) * f - amount * blur in fp32 with
+ * every operation rounded on its own, clamped to [0, 255] and rounded half to even.
+ * ws >= pld_unsharp_u8_workspace_size(n). */
+size_t pld_unsharp_u8_workspace_size(int n);
+int pld_unsharp_u8(const float* x, int n, int h, int w, int normalize, float sigma, float amount,
+                   uint8_t* out_u8, void* ws, void* stream);
+/* metrics.py:9-57 hausdorff_distance and hausdorff_pair on every tile of the two edge maps, as
+ * active_sampling applies them (active_learning_method.py:26-34; tiles in splitImage's row-major
+ * order, preprocess_utils.py:29-42). h == w, h % split == 0 and a tile side t = h / split of at
+ * most PLD_TILE_MAX. With A / B the non-zero pixels of the input / prediction tile,
+ * out[image][tile] = {hd2, in_r, in_c, pred_r, pred_c, n_in, n_pred, branch}:
+ *   hd2     squared Hausdorff distance max(hAB, hBA), hAB = max_a min_b |a - b|^2 and hBA the
+ *           same with the sets swapped; 0 when both sets are empty, -1 when one is (the
+ *           reference's inf)
+ *   branch  1 when hAB > hBA: the input point is the first a in row-major order that attains
+ *           hAB and the prediction point its nearest b; 0 otherwise: the prediction point is the
+ *           first b that attains hBA and the input point its nearest a. Several nearest points:
+ *           the lowest row-major index (the reference leaves this to cKDTree). -1, and -1 for the
+ *           four tile-local coordinates, when a set is empty
+ *   n_in, n_pred  the sizes of A and B */
+int pld_tile_hausdorff(const uint8_t* edges_in, const uint8_t* edges_pred, int n, int h, int w,
+                       int split, int32_t* out, void* stream);
+/* active_learning_method.py:12-17 get_edge_pixel's idx[0][i], idx[1][i]: for every tile with
+ * k[image][tile] >= 0 the tile-local (r, c) of its k-th non-zero pixel in row-major order, (-1, -1)
+ * when the tile holds no more than k; entries of tiles with k < 0 are not written. Limits as
+ * pld_tile_hausdorff. */
+int pld_tile_nth_edge(const uint8_t* edges_in, int n, int h, int w, int split, const int32_t* k,
+                      int32_t* rc, void* stream);
+/* active_learning_method.py:61-76 oracle after its shuffle: pos_xy [n][P][2] (r, c) points,
+ * out [n][P / L][L][2]. Row j holds (r * row_stride + c, gt[r][c]) of points j L .. j L + L - 1
+ * when j L < P - L (the reference's loop bound: with L dividing P the last row stays zero) and
+ * zeros otherwise, sorted by depth descending, equal depths by later position first
+ * (np.argsort(.)[::-1] over a stable sort). L <= PLD_ORACLE_MAX_L. */
+int pld_al_oracle(const float* gt, int n, int h, int w, const int32_t* pos_xy, int P, int L,
+                  int row_stride, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * hipGraph capture of a whole stream-ordered step (replaces Keras' per-op dispatch)
  * ------------------------------------------------------------------------------------------ */
 int pld_graph_begin(void* stream);

@@ -5,8 +5,8 @@ pldepth/models/PLDepthNet.py:1-3, run_scripts/*, hyperopt/*). This package holds
 own: a meta-path finder resolves ``pldepth.X[.Y...]`` to the module object ``pldepth_amd.X[.Y...]``
 (the same object, registered under both names), so ``from pldepth.models.PLDepthNet import
 get_pl_depth_net`` returns this build's factory and a reference driver runs unchanged on the HIP
-path. Names with no counterpart here (wandb/mlflow tracking, hyper-opt, active-learning drivers:
-out of scope) raise the usual ModuleNotFoundError.
+path. Names with no counterpart here (wandb/mlflow tracking, hyper-opt, the run scripts other than
+active_PLDepth: out of scope) raise the usual ModuleNotFoundError.
 """
 import importlib
 import importlib.abc

@@ -145,6 +145,13 @@ _SIGS = {
     "pld_auto_canny_u8": (I32, [P, I32, I32, I32, F64, F64, P, P, P, P, P]),
     "pld_chamfer_dt3": (I32, [P, I32, I32, I32, F32, P, P]),
     "pld_depth_edge_metric": (I32, [P, P, I32, I32, I32, P, P]),
+    "pld_gray_f32": (I32, [P, I32, I64, P, P]),
+    "pld_median_blur_u8": (I32, [P, I32, I32, I32, I32, P, P]),
+    "pld_unsharp_u8_workspace_size": (SZ, [I32]),
+    "pld_unsharp_u8": (I32, [P, I32, I32, I32, I32, F32, F32, P, P, P]),
+    "pld_tile_hausdorff": (I32, [P, P, I32, I32, I32, I32, P, P]),
+    "pld_tile_nth_edge": (I32, [P, I32, I32, I32, I32, P, P, P]),
+    "pld_al_oracle": (I32, [P, I32, I32, I32, P, I32, I32, I32, P, P]),
     "pld_graph_begin": (I32, [P]),
     "pld_graph_end": (I32, [P, C.POINTER(P)]),
     "pld_graph_launch": (I32, [P, P]),
@@ -165,7 +172,8 @@ _NON_STATUS = {"pld_last_error", "pld_version", "pld_pgemm_ok", "pld_conv_num_ti
                "pld_dwconv_dgrad_bn_bwd_workspace_size",
                "pld_dwconv_dgrad_se_bn_workspace_size",
                "pld_filter_refresh_plan",
-               "pld_minmax_u8_workspace_size", "pld_canny_workspace_size"}
+               "pld_minmax_u8_workspace_size", "pld_canny_workspace_size",
+               "pld_unsharp_u8_workspace_size"}
 
 
 def declared_symbols(header=HEADER):

@@ -23,12 +23,59 @@ transform are restatements of its algorithms (unpinned, like ``calc_d``'s normal
 reference's own part (thresholds, the ``> 10`` cut, sums and division) is pinned by
 ``tests/golden/edge_golden.npz``. Reference quirks kept: the distance transform is taken of the
 edge map itself (distance from an edge pixel to the nearest non-edge pixel), and a map without
-edges gives nan. The Hausdorff helpers (cKDTree tie order) are not part of this build.
+edges gives nan.
+
+The Hausdorff helpers of metrics.py:9-57, for one pair of maps of at most 32 x 32 pixels (the
+tiles ``active_sampling`` hands them), run ``pld_tile_hausdorff`` with one tile:
+  * ``hausdorff_distance(image0, image1)`` / ``hausdorf_dist(i1, i2)``   metrics.py:9-28
+  * ``hausdorff_pair(image0, image1)``                                     metrics.py:31-57
+The distance is the square root of an integer and equals the reference's; the pair equals the
+reference's except where the nearest point is not unique: the reference then returns whatever
+cKDTree finds first, this build the lowest row-major index.
 """
+import warnings
+
 import numpy as np
 import torch
 
 from .. import kernels as K
+
+
+def _hausdorff_row(image0, image1):
+    """pld_tile_hausdorff's eight numbers for one pair of (H, H) maps, H <= 32."""
+    maps = []
+    for im in (image0, image1):
+        t = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+        if t.dim() != 2 or t.shape[0] != t.shape[1] or t.shape[0] > K.TILE_MAX:
+            raise ValueError(f"hausdorff: expected a square map of at most {K.TILE_MAX} x "
+                             f"{K.TILE_MAX} pixels, got {tuple(t.shape)}")
+        maps.append((t != 0).to(device="cuda", dtype=torch.uint8).contiguous()[None])
+    if maps[0].shape != maps[1].shape:
+        raise ValueError("hausdorff: the two maps differ in size")
+    return K.tile_hausdorff(maps[0], maps[1], 1)[0, 0].tolist()
+
+
+def hausdorff_distance(image0, image1):
+    """Hausdorff distance between the non-zero pixels of the two maps: 0 when both are empty,
+    inf when one is."""
+    row = _hausdorff_row(image0, image1)
+    if row[0] < 0:
+        return np.inf
+    return 0 if row[5] == 0 else np.sqrt(float(row[0]))
+
+
+def hausdorf_dist(i1, i2):
+    return hausdorff_distance(i1, i2)
+
+
+def hausdorff_pair(image0, image1):
+    """The pair of points (one per map) that are the Hausdorff distance apart, as two int64
+    (r, c) arrays; (), () with a warning when a map is empty."""
+    row = _hausdorff_row(image0, image1)
+    if row[7] < 0:
+        warnings.warn("One or both of the images is empty.", stacklevel=2)
+        return (), ()
+    return np.array(row[1:3], np.int64), np.array(row[3:5], np.int64)
 
 
 def _pairs(imsize, num):

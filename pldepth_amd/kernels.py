@@ -1143,6 +1143,77 @@ def depth_edge_metric(edges_op, edges_gt):
     return out
 
 
+# ---- active-learning selection (active.hip) ----
+MEDIAN_MAX_KSIZE = 15  # PLD_MEDIAN_MAX_KSIZE
+TILE_MAX = 32          # PLD_TILE_MAX: largest tile side of the tile entry points
+ORACLE_MAX_L = 16      # PLD_ORACLE_MAX_L
+
+
+def gray(rgb):
+    """rgb: [n, h, w, 3] float32 device tensor -> [n, h, w] float32 (cv2 RGB2GRAY)."""
+    assert rgb.dim() == 4 and rgb.shape[-1] == 3, tuple(rgb.shape)
+    n, h, w, _ = rgb.shape
+    out = torch.empty((n, h, w), dtype=torch.float32, device=rgb.device)
+    lib().pld_gray_f32(ptr(_f32(rgb)), n, h * w, ptr(out), stream())
+    return out
+
+
+def median_blur(img, ksize):
+    """img: [n, h, w] uint8 device tensor -> cv2.medianBlur(img, ksize) per image."""
+    n, h, w = _u8_maps(img)
+    out = torch.empty_like(img)
+    lib().pld_median_blur_u8(ptr(img), n, h, w, int(ksize), ptr(out), stream())
+    return out
+
+
+def unsharp(x, sigma=1.0, amount=3.0, normalize=True):
+    """x: [n, h, w] float32 device tensor -> [n, h, w] uint8: each map min-max scaled to 0..255
+    as float32 (normalize=False: taken as it is) and sharpened by the reference's
+    unsharp_mask((5, 5), sigma, amount)."""
+    assert x.dim() == 3, tuple(x.shape)
+    n, h, w = x.shape
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    ws = workspace(lib().pld_unsharp_u8_workspace_size(n), "unsharp_u8")
+    lib().pld_unsharp_u8(ptr(_f32(x)), n, h, w, int(bool(normalize)), float(sigma), float(amount),
+                         ptr(out), ptr(ws), stream())
+    return out
+
+
+def tile_hausdorff(edges_in, edges_pred, split):
+    """edges_in, edges_pred: [n, h, h] uint8 edge maps -> [n, split^2, 8] int32 per tile:
+    (hd2, in_r, in_c, pred_r, pred_c, n_in, n_pred, branch), see pld_tile_hausdorff."""
+    n, h, w = _u8_maps(edges_in)
+    assert tuple(edges_pred.shape) == (n, h, w) and edges_pred.dtype == torch.uint8
+    out = torch.empty((n, split * split, 8), dtype=torch.int32, device=edges_in.device)
+    lib().pld_tile_hausdorff(ptr(edges_in), ptr(edges_pred), n, h, w, int(split), ptr(out),
+                             stream())
+    return out
+
+
+def tile_nth_edge(edges_in, split, k, rc):
+    """For tiles with k[image, tile] >= 0, rc[image, tile] = tile-local (r, c) of the tile's k-th
+    non-zero pixel; other entries of rc (int32 [n, split^2, 2]) stay as they are."""
+    n, h, w = _u8_maps(edges_in)
+    assert k.dtype == torch.int32 and tuple(k.shape) == (n, split * split)
+    assert rc.dtype == torch.int32 and tuple(rc.shape) == (n, split * split, 2)
+    lib().pld_tile_nth_edge(ptr(edges_in), n, h, w, int(split), ptr(k), ptr(rc), stream())
+    return rc
+
+
+def al_oracle(gt, pos_xy, L, row_stride):
+    """gt: [n, h, w] float32, pos_xy: [n, P, 2] int32 (r, c) -> [n, P // L, L, 2] float32
+    rankings (flat index r * row_stride + c, depth), see pld_al_oracle."""
+    n, h, w = gt.shape
+    assert pos_xy.dtype == torch.int32 and pos_xy.dim() == 3 and pos_xy.shape[0] == n
+    P = pos_xy.shape[1]
+    out = torch.empty((n, P // L, L, 2), dtype=torch.float32, device=gt.device)
+    if out.numel() == 0:  # fewer points than one ranking
+        return out
+    lib().pld_al_oracle(ptr(_f32(gt)), n, h, w, ptr(pos_xy), P, int(L), int(row_stride), ptr(out),
+                        stream())
+    return out
+
+
 # ---- HR-WSI resizing (pld_resize_bilinear / pld_resize_nearest) ----
 def resize(x, oh, ow, method="bilinear", out=None):
     """x: [n, h, w, c] float32 device tensor -> [n, oh, ow, c] (tf.image.resize, TF2 semantics)."""

@@ -79,6 +79,11 @@ class FullyFledgedModel(object):
         if self.trainer is None:
             raise RuntimeError("compile() the model first")
         tr = self.trainer
+        if self._captured and torch.as_tensor(y).numel() != tr.y_true.numel():
+            # another ranking count than the captured step's (the active-learning round's
+            # second fit, run_scripts/active_PLDepth.py:182): one eager step, then capture again
+            tr.drop_graphs()
+            self._captured = False
         tr.set_batch(x, None, None)
         tr.set_rankings(y)
         if not self._captured:

@@ -142,6 +142,14 @@ class ReplicaTrainer:
             self.y_true.copy_(y.reshape(self.y_true.shape))
             self._keep_alive(y)
 
+    def drop_graphs(self):
+        """Forget the captured step (after everything queued has run): the next step is eager,
+        set_rankings may then take another ranking count, and capture() records the step
+        again."""
+        torch.cuda.synchronize(self.device)
+        self.graphs = None
+        self.bucket_graphs = None
+
     # ------------------------------------------------------------------ phases
     def _sample(self):
         if not self.gpu_sampler:

@@ -149,6 +149,33 @@ int main() {
     EXPECT(pld_chamfer_dt3(img, 1, 2, 2, -1.f, dt, nullptr) == PLD_ERR_ARG);
   }
 
+  // active-learning selection: null checks, then the size limits, refused before any launch
+  EXPECT(pld_unsharp_u8_workspace_size(0) == 0 && pld_unsharp_u8_workspace_size(2) > 0);
+  EXPECT(pld_gray_f32(nullptr, 1, 64, nullptr, nullptr) == PLD_ERR_ARG);
+  EXPECT(pld_median_blur_u8(nullptr, 1, 8, 8, 3, nullptr, nullptr) == PLD_ERR_ARG);
+  EXPECT(pld_unsharp_u8(nullptr, 1, 8, 8, 1, 1.f, 3.f, nullptr, nullptr, nullptr) == PLD_ERR_ARG);
+  EXPECT(pld_tile_hausdorff(nullptr, nullptr, 1, 8, 8, 1, nullptr, nullptr) == PLD_ERR_ARG);
+  EXPECT(pld_tile_nth_edge(nullptr, 1, 8, 8, 1, nullptr, nullptr, nullptr) == PLD_ERR_ARG);
+  EXPECT(pld_al_oracle(nullptr, 1, 8, 8, nullptr, 4, 2, 8, nullptr, nullptr) == PLD_ERR_ARG);
+  {
+    uint8_t img[4] = {0}, out[4] = {0};
+    int32_t tab[8] = {0}, k[1] = {0};
+    float gt[4] = {0}, y[4] = {0};
+    EXPECT(pld_median_blur_u8(img, 1, 2, 2, PLD_MEDIAN_MAX_KSIZE + 2, out, nullptr) ==
+           PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_median_blur_u8(img, 1, 2, 2, 4, out, nullptr) == PLD_ERR_ARG);  // even
+    EXPECT(pld_unsharp_u8(gt, 1, 2, 2, 1, 0.f, 3.f, out, y, nullptr) == PLD_ERR_ARG);  // sigma
+    EXPECT(pld_tile_hausdorff(img, img, 1, PLD_TILE_MAX + 1, PLD_TILE_MAX + 1, 1, tab, nullptr) ==
+           PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_tile_hausdorff(img, img, 1, 64, 48, 2, tab, nullptr) == PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_tile_hausdorff(img, img, 1, 64, 64, 3, tab, nullptr) == PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_tile_hausdorff(img, img, 1, 64, 64, 0, tab, nullptr) == PLD_ERR_ARG);
+    EXPECT(pld_tile_nth_edge(img, 1, 66, 66, 2, k, tab, nullptr) == PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_al_oracle(gt, 1, 2, 2, tab, 40, PLD_ORACLE_MAX_L + 1, 2, y, nullptr) ==
+           PLD_ERR_UNSUPPORTED);
+    EXPECT(pld_al_oracle(gt, 1, 2, 2, tab, 4, 0, 2, y, nullptr) == PLD_ERR_ARG);
+  }
+
   if (failures) {
     std::fprintf(stderr, "%d failures\n", failures);
     return 1;
