@@ -401,9 +401,10 @@ int pld_dropconnect_scales(float* scales, int n, float rate, uint64_t seed, uint
 int pld_dropconnect_scales_dev(float* scales, int n, float rate, uint64_t seed,
                                const int64_t* step_dev, int layer, int image_offset,
                                void* stream);
-/* The same keep factors for nl <= 32 layers in one launch: scales[s * n + i] = the factor of
- * layer layers[s] at rate rates[s] (host arrays); the step from step_dev when it is non-NULL
- * (graph replay), else from step. */
+/* The same keep factors for nl <= PLD_DROPCONNECT_MAX_LAYERS layers in one launch: scales[s * n
+ * + i] = the factor of layer layers[s] at rate rates[s] (host arrays); the step from step_dev
+ * when it is non-NULL (graph replay), else from step. */
+#define PLD_DROPCONNECT_MAX_LAYERS 32
 int pld_dropconnect_scales_multi(float* scales, int n, int nl, const float* rates,
                                  const int* layers, uint64_t seed, uint64_t step,
                                  const int64_t* step_dev, int image_offset, void* stream);

@@ -12,168 +12,115 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PLD_LIB_PATH") or os.path.join(_HERE, "libpldepth_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pldepth_hip.h")
 
-P = C.c_void_p
-I32 = C.c_int
-I64 = C.c_int64
-U64 = C.c_uint64
-F32 = C.c_float
-F64 = C.c_double
-SZ = C.c_size_t
-
 
 class PLDError(RuntimeError):
     pass
 
 
-class ConvArgs(C.Structure):
-    """Mirror of ``pld_conv_args``."""
-    _fields_ = [
-        ("x1", P), ("x2", P), ("c1", I32), ("c2", I32),
-        ("n", I32), ("h", I32), ("w", I32),
-        ("kh", I32), ("kw", I32), ("sh", I32), ("sw", I32), ("pad_t", I32), ("pad_l", I32),
-        ("oh", I32), ("ow", I32), ("cout", I32),
-        ("in_scale", P), ("in_shift", P), ("in_act", I32), ("tile", I32),
-        ("ws", P), ("ws_bytes", SZ), ("math", I32), ("w_split", P),
-    ]
+# ---- the binding is read from include/pldepth_hip.h: plain C, one prototype style, `typedef
+# struct`s, anonymous enums with explicit values and integer #defines. Anything else raises.
+_SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
+            "double": C.c_double, "size_t": C.c_size_t}
+_POINTEES = set(_SCALARS) | {"void", "char", "int32_t", "uint8_t"}
+# structs a caller passes with byref(); any other pointer is a raw address (tensor.data_ptr())
+_BYREF_STRUCTS = {"pld_conv_args"}
+# int-returning functions whose value is an answer rather than a status
+_INT_QUERIES = {"pld_version", "pld_pgemm_ok", "pld_conv_num_tiles", "pld_conv_num_schedules",
+                "pld_conv_schedule_class", "pld_conv_kernel_kind", "pld_sampler_candidates",
+                "pld_filter_refresh_plan"}
 
 
-_SIGS = {
-    "pld_last_error": (C.c_char_p, []),
-    "pld_version": (I32, []),
-    "pld_listmle_fwd_bwd": (I32, [P, P, I32, I32, I32, I32, P, P, P, I32, P]),
-    "pld_adam_amsgrad": (I32, [P, P, P, P, P, I64, F32, F32, F32, F32, I64, F32, P]),
-    "pld_adam_amsgrad_dev": (I32, [P, P, P, P, P, I64, P, P, F32, F32, F32, F32, P]),
-    "pld_step_increment": (I32, [P, P]),
-    "pld_set_scalar_f32": (I32, [P, F32, P]),
-    "pld_sampler_draw_dev": (I32, [P, I32, I32, I32, U64, P, I32, P, P]),
-    "pld_dropconnect_scales_dev": (I32, [P, I32, F32, U64, P, I32, I32, P]),
-    "pld_dropconnect_scales_multi": (I32, [P, I32, I32, P, P, U64, U64, P, I32, P]),
-    "pld_conv2d_fwd": (I32, [C.POINTER(ConvArgs), P, P, P, I32, P]),
-    "pld_conv2d_dgrad": (I32, [C.POINTER(ConvArgs), P, P, P, I32, P, I32, P]),
-    "pld_conv2d_wgrad_workspace_size": (SZ, [C.POINTER(ConvArgs)]),
-    "pld_conv2d_wgrad": (I32, [C.POINTER(ConvArgs), P, P, I32, P, SZ, P]),
-    "pld_conv_num_tiles": (I32, []),
-    "pld_conv2d_fwd_bn_stats_workspace_size": (SZ, [C.POINTER(ConvArgs)]),
-    "pld_conv2d_fwd_bn_stats": (I32, [C.POINTER(ConvArgs), P, P, P, F32, F32, P, P, P, P, P, SZ,
-                                      P]),
-    "pld_conv_num_schedules": (I32, [I32]),
-    "pld_conv_schedule_class": (I32, [I32, I32]),
-    "pld_conv_schedule_desc": (C.c_char_p, [I32, I32]),
-    "pld_conv_kernel_kind": (I32, [C.POINTER(ConvArgs), I32]),
-    "pld_conv_kernel_name": (C.c_char_p, [C.POINTER(ConvArgs), I32]),
-    "pld_conv2d_fwd_workspace_size": (SZ, [C.POINTER(ConvArgs)]),
-    "pld_conv2d_dgrad_workspace_size": (SZ, [C.POINTER(ConvArgs)]),
-    "pld_filter_to_native": (I32, [P, I32, I32, I32, I32, P, P]),
-    "pld_filter_split": (I32, [P, I64, I32, P, P]),
-    "pld_filter_to_dgrad": (I32, [P, I32, I32, I32, I32, P, P]),
-    "pld_filter_refresh": (I32, [P, I32, I32, I32, I32, P, P, P, P, P]),
-    "pld_filter_refresh_plan": (I32, [I32, I32, I32, I32, P, P, P, P, P]),
-    "pld_filter_refresh_multi": (I32, [P, I32, I32, P]),
-    "pld_channel_reduce_workspace_size": (SZ, [I64, I32]),
-    "pld_channel_sum": (I32, [P, I64, I32, P, I32, P, P]),
-    "pld_bn_stats": (I32, [P, I64, I32, F32, F32, P, P, P, P, P, P]),
-    "pld_bn_apply": (I32, [P, I64, I32, P, P, P, P, I32, P, I32, P, P]),
-    "pld_bn_bwd": (I32, [P, P, I64, I32, P, P, P, P, I32, P, P, I32, P, I32, P, P, I32, P, P]),
-    "pld_channel_affine_act": (I32, [P, I64, I32, P, P, I32, P, P]),
-    "pld_bn_bwd_coeffs": (I32, [P, P, I64, I32, P, P, P, P, I32, P, P, I32, P, P, P]),
-    "pld_pgemm_ok": (I32, [I32, I32]),
-    "pld_pgemm_bn_act": (I32, [P, I64, I32, P, P, P, P, I32, P, I32, P, I32, P, I32, P]),
-    "pld_pgemm_bn_bwd": (I32, [P, P, I64, I32, P, P, P, P, I32, P, P, I32, P, I32, P]),
-    "pld_bn_add_apply": (I32, [P, I64, I32, P, P, P, P, P, I32, P, P]),
-    "pld_bn_scale_add_apply": (I32, [P, I64, I32, P, P, P, P, P, I32, P, I32, P, P]),
-    "pld_bn_bwd_scaled": (I32, [P, P, I64, I32, P, P, P, P, I32, P, I32, P, I32, P, P, I32, P,
-                                P]),
-    "pld_bn_add_bwd": (I32, [P, P, I64, I32, P, P, P, P, P, I32, P, I32, P, I32, P, P, I32, P,
-                             P]),
-    "pld_maxpool2d_fwd": (I32, [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P]),
-    "pld_maxpool2d_bwd": (I32, [P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, I32,
-                                P]),
-    "pld_upsample2x_fwd": (I32, [P, I32, I32, I32, I32, P, P]),
-    "pld_upsample2x_fwd_bn": (I32, [P, I32, I32, I32, I32, P, P, P, P, I32, P, P]),
-    "pld_upsample2x_bwd": (I32, [P, I32, I32, I32, I32, P, I32, P]),
-    "pld_upconv_wgrad_workspace_size": (SZ, [I32]),
-    "pld_upconv_bwd_workspace_size": (SZ, [I32]),
-    "pld_upconv_bwd": (I32, [P, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P, I32, P, P, I32, P,
-                             SZ, P]),
-    "pld_upconv_fwd": (I32, [P, I32, I32, I32, I32, P, P, P, P, P, P, P, P]),
-    "pld_upconv_wgrad": (I32, [P, I32, I32, I32, I32, P, P, P, P, P, P, P, SZ, P]),
-    "pld_upconv_dgrad": (I32, [P, I32, I32, I32, I32, P, P, P]),
-    "pld_residual_add": (I32, [P, P, P, I32, I64, P, P]),
-    "pld_scale_per_sample": (I32, [P, P, I32, I64, P, I32, P]),
-    "pld_dropconnect_scales": (I32, [P, I32, F32, U64, U64, I32, I32, P]),
-    "pld_bn_inference_coeffs": (I32, [P, P, P, P, I32, F32, P, P, P]),
-    "pld_bn_train_coeffs": (I32, [P, P, P, P, I32, P, P, P]),
-    "pld_channel_pad_affine": (I32, [P, I64, I32, I32, P, P, P, P]),
-    "pld_dwconv_fwd": (I32, [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, P, P]),
-    "pld_dwconv_fwd_bn": (I32, [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, P, P, P,
-                                P, I32, P, P]),
-    "pld_dwconv_fwd_bn_stats_workspace_size": (SZ, [I32, I32, I32, I32, I32]),
-    "pld_dwconv_fwd_bn_stats": (I32, [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, P,
-                                      P, P, P, I32, P, F32, F32, P, P, P, P, P, SZ, P]),
-    "pld_dwconv_dgrad": (I32, [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, P, I32, P]),
-    "pld_dwconv_dgrad_bn_bwd_workspace_size": (SZ, [I32, I32, I32, I32, I32]),
-    "pld_dwconv_dgrad_bn_bwd": (I32, [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, P,
-                                      I32, P, P, P, P, P, I32, P, I32, P, P, I32, P, P, SZ, P]),
-    "pld_se_workspace_size": (SZ, [I32, I32, I32, I32]),
-    "pld_se_fwd": (I32, [P, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P]),
-    "pld_se_bwd": (I32, [P, P, I32, I32, I32, I32, P, P, P, P, P, P, P]),
-    "pld_se_fwd_bn": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P]),
-    "pld_se_bwd_bn": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, P]),
-    "pld_se_bwd_bn_full_workspace_size": (SZ, [I32, I32, I32, I32]),
-    "pld_se_bwd_bn_full": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, I32,
-                                 P, P, I32, P, SZ, P]),
-    "pld_se_bwd_bn_coeffs": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, P,
-                                   I32, P, P, SZ, P]),
-    "pld_dwconv_dgrad_se_bn_workspace_size": (SZ, [I32, I32, I32, I32]),
-    "pld_dwconv_dgrad_se_bn": (I32, [P, P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, P, P, P,
-                                     P, P, I32, P, P, P, I32, P, P, P, P, P, I32, P, P, I32, P, P,
-                                     P, SZ, P]),
-    "pld_sampler_workspace_size": (SZ, [I32, I32, I32, I32, I32, I32]),
-    "pld_sampler_compact": (I32, [P, I32, I32, I32, P, P, P, P, P, P]),
-    "pld_sampler_compact_workspace_size": (SZ, [I32, I32, I32]),
-    "pld_sampler_draw": (I32, [P, I32, I32, I32, U64, U64, I32, P, P]),
-    "pld_sampler_rank": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, P, P, P]),
-    "pld_sampler_candidates": (I32, [I32, I32]),
-    "pld_resize_bilinear": (I32, [P, I32, I32, I32, I32, I32, I32, P, P]),
-    "pld_resize_nearest": (I32, [P, I32, I32, I32, I32, I32, I32, P, P]),
-    "pld_ordinal_error": (I32, [P, P, I32, I64, P, P, I32, P, P]),
-    "pld_dcg_ratio": (I32, [P, P, I32, I64, P, I32, P, P]),
-    "pld_minmax_u8_workspace_size": (SZ, [I32]),
-    "pld_minmax_u8": (I32, [P, I32, I64, P, P, P]),
-    "pld_canny_workspace_size": (SZ, [I32, I32, I32]),
-    "pld_canny_u8": (I32, [P, I32, I32, I32, I32, I32, P, P, P, P]),
-    "pld_auto_canny_u8": (I32, [P, I32, I32, I32, F64, F64, P, P, P, P, P]),
-    "pld_chamfer_dt3": (I32, [P, I32, I32, I32, F32, P, P]),
-    "pld_depth_edge_metric": (I32, [P, P, I32, I32, I32, P, P]),
-    "pld_gray_f32": (I32, [P, I32, I64, P, P]),
-    "pld_median_blur_u8": (I32, [P, I32, I32, I32, I32, P, P]),
-    "pld_unsharp_u8_workspace_size": (SZ, [I32]),
-    "pld_unsharp_u8": (I32, [P, I32, I32, I32, I32, F32, F32, P, P, P]),
-    "pld_tile_hausdorff": (I32, [P, P, I32, I32, I32, I32, P, P]),
-    "pld_tile_nth_edge": (I32, [P, I32, I32, I32, I32, P, P, P]),
-    "pld_al_oracle": (I32, [P, I32, I32, I32, P, I32, I32, I32, P, P]),
-    "pld_graph_begin": (I32, [P]),
-    "pld_graph_end": (I32, [P, C.POINTER(P)]),
-    "pld_graph_launch": (I32, [P, P]),
-    "pld_graph_destroy": (I32, [P]),
-}
+def _ctype(decl, structs, ret=False):
+    """The ctypes type of the C type `decl` ("const float*", "size_t", "void**", ...)."""
+    words = decl.replace("*", " ").split()
+    base = [w for w in words if w != "const"]
+    depth = decl.count("*")
+    if len(base) != 1 or (base[0] not in _POINTEES and base[0] not in structs):
+        raise PLDError(f"pldepth_hip.h: unknown type {decl!r}")
+    base = base[0]
+    if depth == 0:
+        if base not in _SCALARS:
+            raise PLDError(f"pldepth_hip.h: type {decl!r} cannot be passed by value")
+        return _SCALARS[base]
+    if ret and base == "char" and depth == 1:
+        return C.c_char_p
+    if base in _BYREF_STRUCTS and depth == 1:
+        return C.POINTER(structs[base])
+    if base == "void" and depth == 2:
+        return C.POINTER(C.c_void_p)
+    return C.c_void_p
 
+
+def _named(decl, stmt):
+    """("type", "name") of one parameter or field declarator ("const float* x": the header
+    writes the stars with the type)."""
+    typ, _, name = decl.strip().rpartition(" ")
+    if not typ or not name.isidentifier():
+        raise PLDError(f"pldepth_hip.h: cannot parse {decl!r} in {stmt!r}")
+    return typ, name
+
+
+def parse_header(text):
+    """(structs, sigs, consts) of a header in pldepth_hip.h's style: ctypes Structure classes by
+    C name, {function: (restype, argtypes)} and {enumerator or #define: int}."""
+    structs, sigs, consts = {}, {}, {}
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body, skip = [], []  # skip: one flag per open #if; the C++ linkage block is not C
+    for line in text.splitlines():
+        d = line.split()
+        if not d or d[0][0] != "#":
+            if not any(skip):
+                body.append(line)
+        elif d[0] in ("#ifdef", "#ifndef"):
+            skip.append(d[1] == "__cplusplus")
+        elif d[0] == "#endif" and skip:
+            skip.pop()
+        elif d[0] == "#define" and len(d) == 3 and re.fullmatch(r"-?\d+", d[2]):
+            consts[d[1]] = int(d[2])
+        elif not (d[0] == "#include" or (d[0] == "#define" and len(d) == 2)):
+            raise PLDError(f"pldepth_hip.h: cannot parse {line.strip()!r}")
+    # statements end at a ';' outside braces (one level: enum and struct bodies)
+    body, end = "\n".join(body), 0
+    stmts = list(re.finditer(r"((?:[^;{}]|\{[^{}]*\})*);", body))
+    for m in stmts:
+        if m.start() != end:
+            break
+        end = m.end()
+    if body[end:].strip():
+        rest = " ".join(body[end:].split())
+        raise PLDError(f"pldepth_hip.h: unterminated declaration {rest[:200]!r}")
+    for stmt in (" ".join(m.group(1).split()) for m in stmts):
+        m = re.fullmatch(r"enum \{(.*)\}", stmt)
+        if m:
+            for item in m.group(1).split(","):
+                e = re.fullmatch(r"\s*(\w+) = (-?\d+)\s*", item)
+                if not e:
+                    raise PLDError(f"pldepth_hip.h: enumerator without a value in {stmt!r}")
+                consts[e.group(1)] = int(e.group(2))
+            continue
+        m = re.fullmatch(r"typedef struct (\w+) \{(.*)\} \1", stmt)
+        if m:
+            fields = []
+            for decl in filter(str.strip, m.group(2).split(";")):
+                first, *more = decl.split(",")
+                typ, name = _named(first, stmt)
+                fields += [(n.strip(), _ctype(typ, structs)) for n in [name] + more]
+            structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields})
+            continue
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(pld_\w+)\s*\(([\w\s*,]*)\)", stmt)
+        if not m:
+            raise PLDError(f"pldepth_hip.h: cannot parse declaration {stmt!r}")
+        params = [] if m.group(3).strip() == "void" else m.group(3).split(",")
+        sigs[m.group(2)] = (_ctype(m.group(1), structs, ret=True),
+                            [_ctype(_named(q, stmt)[0], structs) for q in params])
+    return structs, sigs, consts
+
+
+_STRUCTS, _SIGS, CONST = parse_header(open(HEADER).read())
+ConvArgs = _STRUCTS["pld_conv_args"]
+RefreshDesc = _STRUCTS["pld_filter_refresh_desc"]
 # functions returning a value rather than a status
-_NON_STATUS = {"pld_last_error", "pld_version", "pld_pgemm_ok", "pld_conv_num_tiles", "pld_conv_num_schedules",
-               "pld_conv_schedule_class", "pld_conv_schedule_desc",
-               "pld_conv_kernel_kind", "pld_conv_kernel_name",
-               "pld_conv2d_fwd_workspace_size", "pld_conv2d_dgrad_workspace_size", "pld_conv2d_wgrad_workspace_size",
-               "pld_conv2d_fwd_bn_stats_workspace_size",
-               "pld_dwconv_fwd_bn_stats_workspace_size",
-               "pld_channel_reduce_workspace_size", "pld_se_workspace_size",
-               "pld_sampler_workspace_size", "pld_sampler_candidates",
-               "pld_sampler_compact_workspace_size", "pld_upconv_wgrad_workspace_size",
-               "pld_upconv_bwd_workspace_size", "pld_se_bwd_bn_full_workspace_size",
-               "pld_dwconv_dgrad_bn_bwd_workspace_size",
-               "pld_dwconv_dgrad_se_bn_workspace_size",
-               "pld_filter_refresh_plan",
-               "pld_minmax_u8_workspace_size", "pld_canny_workspace_size",
-               "pld_unsharp_u8_workspace_size"}
+_NON_STATUS = {n for n, (res, _) in _SIGS.items() if res is not C.c_int or n in _INT_QUERIES}
 
 
 def declared_symbols(header=HEADER):

@@ -143,3 +143,33 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 }  // namespace pld
+
+// ---- cross-file helpers (pld__*): one prototype each, seen by the defining file and by every
+// caller, so a definition that drifts from it is a compile error. Hidden: the library exports
+// only what include/pldepth_hip.h declares.
+#define PLD_INTERNAL extern "C" __attribute__((visibility("hidden")))
+
+// bn.hip: BN batch statistics from channel-major fp64 partials (stats_finalize_kernel)
+PLD_INTERNAL int pld__bn_stats_finish(const double* part, int nparts, int64_t rows, int c,
+                                      float eps, float momentum, float* mean, float* invstd,
+                                      float* moving_mean, float* moving_var, hipStream_t st);
+// bn.hip: finalize (dgamma, dbeta, k1, k2 from channel-major partials) + apply
+PLD_INTERNAL int pld__bn_bwd_finish(const double* part, int nparts, const float* x,
+                                    const float* dy, int64_t rows, int c, const float* mean,
+                                    const float* invstd, const float* gamma, const float* beta,
+                                    int act, const float* gate, const float* addn, int hw,
+                                    float* dx, int dx_accumulate, float* dgamma, float* dbeta,
+                                    int param_accumulate, float* k12, hipStream_t st);
+// dwtile.hip: the LDS-tiled depthwise forward (C % 16 == 0), optionally gathering the output's
+// BN partials, and the stride-1 input gradient through the same kernel
+PLD_INTERNAL int pld__dw_tiled_ok(int k, int s, int c);
+PLD_INTERNAL int pld__dw_tiled_parts(int n, int oh, int ow, int s, int c);
+PLD_INTERNAL int pld__dw_dgrad_tiled(const float* dy, int n, int h, int w, int c,
+                                     const float* wdw, int k, int pad_t, int pad_l, int oh,
+                                     int ow, float* dx, int accumulate, const float* const* pro,
+                                     const float* const* epi, double* part, hipStream_t st);
+PLD_INTERNAL int pld__dw_fwd_tiled(const float* x, int n, int h, int w, int c, const float* wdw,
+                                   int k, int s, int pad_t, int pad_l, int oh, int ow,
+                                   const float* mean, const float* invstd, const float* gamma,
+                                   const float* beta, int act, float* y, double* stats,
+                                   hipStream_t st);

@@ -290,3 +290,61 @@ __device__ __forceinline__ void store_acc(const GemmConvParams& p, const floatx1
 }
 
 }  // namespace pld
+
+// ---- cross-file conv helpers called by the dispatch in conv_igemm.hip (PLD_INTERNAL: common.h)
+// skinny.hip: direct kernels for the 1 -> 1 channel 1x1 and the single-output-channel 3x3 conv
+PLD_INTERNAL int pld__scalar1x1_eligible(const pld_conv_args* a);
+PLD_INTERNAL int pld__scalar1x1_apply(const float* x, const float* w, const float* bias, float* y,
+                                      long n, int accumulate, void* stream);
+PLD_INTERNAL size_t pld__scalar1x1_wgrad_ws(void);
+PLD_INTERNAL int pld__scalar1x1_wgrad(const float* x, const float* dy, float* dw, long n,
+                                      int accumulate, void* ws, void* stream);
+PLD_INTERNAL int pld__skinny_eligible(const pld_conv_args* a);
+PLD_INTERNAL int pld__skinny_fwd(const pld_conv_args* a, const float* w_ohwi, const float* bias,
+                                 float* y, int accumulate, void* stream);
+PLD_INTERNAL int pld__skinny_dgrad(const pld_conv_args* a, const float* dy, const float* w_dgrad,
+                                   float* dx, int accumulate, void* stream);
+PLD_INTERNAL size_t pld__skinny_wgrad_ws(const pld_conv_args* a);
+PLD_INTERNAL int pld__skinny_wgrad(const pld_conv_args* a, const float* dy, float* dw,
+                                   int accumulate, void* ws, void* stream);
+// stem.hip: the EfficientNetB0 stem conv (3 -> 32 channels, 3x3 stride 2) with its BN partials
+PLD_INTERNAL int pld__stem3x3_eligible(const pld_conv_args* a);
+PLD_INTERNAL int pld__stem3x3_parts(const pld_conv_args* a);
+PLD_INTERNAL int pld__stem3x3_fwd(const pld_conv_args* a, const float* w_nat, const float* bias,
+                                  float* y, int accumulate, double* stats, void* stream);
+// thin.hip: exact fp32 1x1 GEMM for short reductions (K <= 48), HBM-bound
+PLD_INTERNAL int pld__thin_ok(int K, int N);
+PLD_INTERNAL int pld__thin_geom(const pld_conv_args* a);
+PLD_INTERNAL int pld__thin_gemm(const float* a, const float* b, const float* bias, float* out,
+                                long M, int K, int N, int acc, void* stream, double* stats);
+PLD_INTERNAL int pld__thin_stats_parts(long M);
+// wide1x1.hip: streaming bf16x3 1x1 GEMM for short reductions into wide outputs
+PLD_INTERNAL int pld__wide_ok(int K, int N);
+PLD_INTERNAL int pld__wide_stats_parts(long M, int K, int N);
+PLD_INTERNAL int pld__wide_gemm(const float* a, const float* w, const float* bias, float* out,
+                                long M, int K, int N, int acc, void* stream, double* stats);
+// conv_x3.hip: bf16x3 tiles, tile stream and patch kernels
+PLD_INTERNAL int pld__x3_num_cfg(void);
+PLD_INTERNAL int pld__x3_cfg_dims(int cfg, int* bm, int* bn, int* tm, int* tn, int* occ);
+PLD_INTERNAL int pld__x3_wgrad_cfg_ok(int cfg);
+PLD_INTERNAL int pld__x3_launch(pld::GemmConvParams* p, int mode, int splits, int cfg,
+                                int sk_grid, void* stream);
+PLD_INTERNAL int pld__x3_num_patch(void);
+PLD_INTERNAL int pld__x3_patch_bn(int cfg);
+PLD_INTERNAL int pld__x3_patch_ok(const pld::GemmConvParams* p, int cfg);
+PLD_INTERNAL int pld__x3_patch_launch(pld::GemmConvParams* p, int cfg, void* stream);
+PLD_INTERNAL int pld__x3_patch_wgrad_ok(const pld::GemmConvParams* p);
+PLD_INTERNAL int pld__x3_patch_wgrad_cw(int N);
+PLD_INTERNAL int pld__x3_patch_wgrad_th(int N);
+PLD_INTERNAL int pld__x3_patch_wgrad_tiles(const pld::GemmConvParams* p);
+PLD_INTERNAL int pld__x3_patch_wgrad_launch(pld::GemmConvParams* p, int splits, void* stream);
+// conv_x3_halo.hip: bf16x3 row-band halo kernel
+PLD_INTERNAL int pld__x3_num_halo(void);
+PLD_INTERNAL int pld__x3_halo_dims(int cfg, int* bm, int* bn, int* tm, int* tn);
+PLD_INTERNAL int pld__x3_halo_ok(const pld::GemmConvParams* p);
+PLD_INTERNAL int pld__x3_halo_wmax(int cfg);
+PLD_INTERNAL int pld__x3_halo_occ2(int cfg);
+PLD_INTERNAL int pld__x3_halo_launch(pld::GemmConvParams* p, int cfg, int splits, int sk_grid,
+                                     void* stream);
+PLD_INTERNAL int pld__x3_halo_stream_plan(pld::GemmConvParams* p, int cfg);
+PLD_INTERNAL size_t pld__x3_halo_stream_slab_bytes(int cfg, int G, int aligned);

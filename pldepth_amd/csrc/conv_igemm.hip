@@ -872,69 +872,14 @@ static int fill_geom(const pld_conv_args* a, GemmConvParams& p) {
 
 using namespace pld;
 
-// direct kernels for the single-output-channel 3x3 conv and the 1 -> 1 channel 1x1 (skinny.hip)
-extern "C" int pld__scalar1x1_eligible(const pld_conv_args* a);
-extern "C" int pld__scalar1x1_apply(const float* x, const float* w, const float* bias, float* y,
-                                    long n, int accumulate, void* stream);
-extern "C" size_t pld__scalar1x1_wgrad_ws(void);
-extern "C" int pld__scalar1x1_wgrad(const float* x, const float* dy, float* dw, long n,
-                                    int accumulate, void* ws, void* stream);
-extern "C" int pld__skinny_eligible(const pld_conv_args* a);
-extern "C" int pld__stem3x3_eligible(const pld_conv_args* a);
-extern "C" int pld__stem3x3_parts(const pld_conv_args* a);
-extern "C" int pld__stem3x3_fwd(const pld_conv_args* a, const float* w_nat, const float* bias,
-                                float* y, int accumulate, double* stats, void* stream);
-extern "C" int pld__skinny_fwd(const pld_conv_args* a, const float* w_ohwi, const float* bias,
-                               float* y, int accumulate, void* stream);
-extern "C" int pld__skinny_dgrad(const pld_conv_args* a, const float* dy, const float* w_dgrad,
-                                 float* dx, int accumulate, void* stream);
-extern "C" size_t pld__skinny_wgrad_ws(const pld_conv_args* a);
-extern "C" int pld__skinny_wgrad(const pld_conv_args* a, const float* dy, float* dw,
-                                 int accumulate, void* ws, void* stream);
+// the direct, thin, wide, bf16x3 and BN helpers of the other files: conv_common.h, common.h
 
-// bf16x3 kernels (conv_x3.hip)
-extern "C" int pld__thin_ok(int K, int N);
-extern "C" int pld__thin_geom(const pld_conv_args* a);
-extern "C" int pld__thin_gemm(const float* a, const float* b, const float* bias, float* out,
-                              long M, int K, int N, int acc, void* stream, double* stats);
-extern "C" int pld__thin_stats_parts(long M);
-// wide1x1.hip: streaming bf16x3 1x1 GEMM for short reductions into wide outputs
-extern "C" int pld__wide_ok(int K, int N);
-extern "C" int pld__wide_stats_parts(long M, int K, int N);
-extern "C" int pld__wide_gemm(const float* a, const float* w, const float* bias, float* out,
-                              long M, int K, int N, int acc, void* stream, double* stats);
 // a bf16x3 1x1 conv whose GEMM (fwd K = cin, N = cout; dgrad K = cout, N = cin) takes the wide
 // kernel: unstrided single-source geometry that the exact thin kernel does not cover
 static bool wide_conv(const pld_conv_args* a, int K, int N) {
   return a->math == PLD_MATH_BF16X3 && pld__thin_geom(a) && !pld__thin_ok(K, N) &&
          pld__wide_ok(K, N) && aligned16(a->x1);
 }
-// bn.hip: BN batch statistics from channel-major fp64 partials (stats_finalize_kernel)
-extern "C" int pld__bn_stats_finish(const double* part, int nparts, int64_t rows, int c,
-                                    float eps, float momentum, float* mean, float* invstd,
-                                    float* moving_mean, float* moving_var, hipStream_t st);
-extern "C" int pld__x3_num_cfg(void);
-extern "C" int pld__x3_cfg_dims(int cfg, int* bm, int* bn, int* tm, int* tn, int* occ);
-extern "C" int pld__x3_wgrad_cfg_ok(int cfg);
-extern "C" int pld__x3_launch(GemmConvParams* p, int mode, int splits, int cfg, int sk_grid,
-                              void* stream);
-extern "C" int pld__x3_num_patch(void);
-extern "C" int pld__x3_patch_bn(int cfg);
-extern "C" int pld__x3_patch_ok(const GemmConvParams* p, int cfg);
-extern "C" int pld__x3_patch_launch(GemmConvParams* p, int cfg, void* stream);
-extern "C" int pld__x3_patch_wgrad_ok(const GemmConvParams* p);
-extern "C" int pld__x3_patch_wgrad_launch(GemmConvParams* p, int splits, void* stream);
-extern "C" int pld__x3_patch_wgrad_cw(int N);
-extern "C" int pld__x3_patch_wgrad_th(int N);
-extern "C" int pld__x3_num_halo(void);
-extern "C" int pld__x3_halo_dims(int cfg, int* bm, int* bn, int* tm, int* tn);
-extern "C" int pld__x3_halo_ok(const GemmConvParams* p);
-extern "C" int pld__x3_halo_wmax(int cfg);
-extern "C" int pld__x3_halo_occ2(int cfg);
-extern "C" int pld__x3_halo_launch(GemmConvParams* p, int cfg, int splits, int sk_grid,
-                                   void* stream);
-extern "C" int pld__x3_halo_stream_plan(GemmConvParams* p, int cfg);
-extern "C" size_t pld__x3_halo_stream_slab_bytes(int cfg, int G, int aligned);
 constexpr int X3_BK = 32;
 // bytes of a pre-split [N][K] filter (same size as fp32), 256-byte aligned
 static size_t x3_split_bytes(long N, long K) { return ((size_t)N * K * 4 + 255) / 256 * 256; }
@@ -987,7 +932,6 @@ static void resolve_sched(int math, bool geom_ok, int tile, bool& x3, int& t,
 static bool x3_wgrad_geom(int c1, int c2, int cout, bool prologue) {
   return c1 % 16 == 0 && c2 % 16 == 0 && cout % 16 == 0 && !prologue;
 }
-extern "C" int pld_filter_split(const float* w, int64_t rows, int K, void* out, void* stream);
 
 // the x3 analogue of choose_tile (same cost model; WGRAD takes power-of-two tiles only)
 static int x3_choose(long M, long N, long K, int requested, bool wgrad) {

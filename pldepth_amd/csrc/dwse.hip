@@ -717,23 +717,6 @@ static DwGeom dw_geom(int n, int h, int w, int c, int s, int pt, int pl, int oh,
   return g;
 }
 
-// dwtile.hip: the LDS-tiled forward (C % 16 == 0), optionally gathering the output's BN partials
-extern "C" int pld__dw_tiled_ok(int k, int s, int c);
-extern "C" int pld__dw_tiled_parts(int n, int oh, int ow, int s, int c);
-extern "C" int pld__dw_dgrad_tiled(const float* dy, int n, int h, int w, int c, const float* wdw,
-                                   int k, int pad_t, int pad_l, int oh, int ow, float* dx,
-                                   int accumulate, const float* const* pro,
-                                   const float* const* epi, double* part, hipStream_t st);
-extern "C" int pld__dw_fwd_tiled(const float* x, int n, int h, int w, int c, const float* wdw,
-                                 int k, int s, int pad_t, int pad_l, int oh, int ow,
-                                 const float* mean, const float* invstd, const float* gamma,
-                                 const float* beta, int act, float* y, double* stats,
-                                 hipStream_t st);
-// bn.hip
-extern "C" int pld__bn_stats_finish(const double* part, int nparts, int64_t rows, int c,
-                                    float eps, float momentum, float* mean, float* invstd,
-                                    float* moving_mean, float* moving_var, hipStream_t st);
-
 template <int K, int S, int T, int R>
 static void dw_fwd_launch(const float* x, const float* wdw, DwGeom& g, float* y, hipStream_t st) {
   const int rgroups = (g.oh + R - 1) / R;
@@ -916,13 +899,6 @@ static bool dw_dgrad_tiled_ok(const float* dy, int n, int h, int w, int c, const
          aligned16(dx) && aligned16(wdw);
 }
 
-extern "C" int pld__bn_bwd_finish(const double* part, int nparts, const float* x, const float* dy,
-                                  int64_t rows, int c, const float* mean, const float* invstd,
-                                  const float* gamma, const float* beta, int act,
-                                  const float* gate, const float* addn, int hw, float* dx,
-                                  int dx_accumulate, float* dgamma, float* dbeta,
-                                  int param_accumulate, float* k12, hipStream_t st);
-
 extern "C" int pld_dwconv_dgrad_bn_bwd(const float* dy, int n, int h, int w, int c,
                                        const float* wdw, int k, int s, int pad_t, int pad_l,
                                        int oh, int ow, float* dact, int accumulate,
@@ -1033,14 +1009,6 @@ extern "C" int pld_se_bwd_bn(const float* dy, const float* x, const float* mean,
   return se_bwd_impl(dy, x, SePro{mean, invstd, gamma, beta, act}, n, hw, c, cse, w1, w2, z1,
                      gate, addn, ws, stream);
 }
-
-// bn.hip: finalize (dgamma, dbeta, k1, k2 from channel-major partials) + apply
-extern "C" int pld__bn_bwd_finish(const double* part, int nparts, const float* x, const float* dy,
-                                  int64_t rows, int c, const float* mean, const float* invstd,
-                                  const float* gamma, const float* beta, int act,
-                                  const float* gate, const float* addn, int hw, float* dx,
-                                  int dx_accumulate, float* dgamma, float* dbeta,
-                                  int param_accumulate, float* k12, hipStream_t st);
 
 // The BN-backward squeeze (img_chan_sum_kernel<true, true>) holds 136 VGPRs, i.e. 3 workgroups
 // per CU: se_rsplit's 1024-workgroup grid ran as 1.33 rounds of the 768 the chip holds at once.

@@ -325,10 +325,9 @@ __global__ void dropconnect_kernel(float* __restrict__ sc, int n, float rate, ui
 }
 
 // every drop-connect layer of one step in one launch: blockIdx.y = layer slot
-constexpr int DC_MAX_LAYERS = 32;
 struct DcLayers {
-  float rate[DC_MAX_LAYERS];
-  int layer[DC_MAX_LAYERS];
+  float rate[PLD_DROPCONNECT_MAX_LAYERS];
+  int layer[PLD_DROPCONNECT_MAX_LAYERS];
 };
 __global__ void dropconnect_multi_kernel(float* __restrict__ sc, int n, DcLayers L, uint64_t seed,
                                          uint64_t step_arg, const int64_t* __restrict__ step_dev,
@@ -430,8 +429,9 @@ extern "C" int pld_dropconnect_scales_multi(float* scales, int n, int nl, const 
                                             const int* layers, uint64_t seed, uint64_t step,
                                             const int64_t* step_dev, int image_offset,
                                             void* stream) {
-  PLD_CHECK_ARG(scales && rates && layers && n > 0 && nl > 0 && nl <= DC_MAX_LAYERS,
-                "pld_dropconnect_scales_multi: bad args");
+  PLD_CHECK_ARG(
+      scales && rates && layers && n > 0 && nl > 0 && nl <= PLD_DROPCONNECT_MAX_LAYERS,
+      "pld_dropconnect_scales_multi: bad args");
   DcLayers L{};
   for (int s = 0; s < nl; ++s) {
     PLD_CHECK_ARG(rates[s] >= 0.f && rates[s] < 1.f, "pld_dropconnect_scales_multi: bad rate");

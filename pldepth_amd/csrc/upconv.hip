@@ -386,14 +386,6 @@ static size_t bn_bytes(int c) { return sizeof(double) * 2 * (size_t)BWD_BLOCKS *
 
 using namespace pld;
 
-// bn.hip: finalize (dgamma, dbeta, k1, k2 from channel-major partials) + apply
-extern "C" int pld__bn_bwd_finish(const double* part, int nparts, const float* x, const float* dy,
-                                  int64_t rows, int c, const float* mean, const float* invstd,
-                                  const float* gamma, const float* beta, int act,
-                                  const float* gate, const float* addn, int hw, float* dx,
-                                  int dx_accumulate, float* dgamma, float* dbeta,
-                                  int param_accumulate, float* k12, hipStream_t st);
-
 extern "C" size_t pld_upconv_bwd_workspace_size(int c) {
   if (c <= 0) return 0;
   return upc::dw_bytes(c) + upc::bn_bytes(c) + 2 * sizeof(float) * (size_t)c + 64;

@@ -11,10 +11,13 @@ import numpy as np
 
 import torch
 
-from ._lib import ConvArgs, lib
+from ._lib import CONST, ConvArgs, RefreshDesc as _RefreshDesc, lib
 
-ACT = {"none": 0, "linear": 0, None: 0, "relu": 1, "swish": 2, "sigmoid": 3}
-SAMPLER = {"pure": 0, "masked": 1, "thresh": 2, "info": 3}
+# selectors and limits of the C ABI, by their names in include/pldepth_hip.h
+ACT = {k: CONST["PLD_ACT_" + v] for k, v in {
+    "none": "NONE", "linear": "NONE", None: "NONE", "relu": "RELU", "swish": "SWISH",
+    "sigmoid": "SIGMOID"}.items()}
+SAMPLER = {k: CONST["PLD_SAMPLER_" + k.upper()] for k in ("pure", "masked", "thresh", "info")}
 
 
 def ptr(t):
@@ -171,7 +174,7 @@ def same_pads(h, k, s):
 # conv product arithmetic (pld_conv_args.math): "bf16x3" (fp32 via three bf16 MFMA products,
 # ~1e-5 relative per product) or "fp32" (exact fp32 MFMA). The model engines apply a policy
 # (below); PLD_CONV_MATH overrides the default one.
-MATH = {"fp32": 0, "bf16x3": 1}
+MATH = {k: CONST["PLD_MATH_" + k.upper()] for k in ("fp32", "bf16x3")}
 # conv arithmetic policies: "auto" (default) = decoder bf16x3, encoder bf16x3
 # where the BN after the conv normalises over >= X3_MIN_POPULATION values per channel, exact
 # fp32 below (BN over a handful of pixels amplifies any rounding); "mixed" = encoder fp32,
@@ -375,20 +378,22 @@ def _schedules(mode, math, a=None):
     split, so only the tiles (and tile streams). Under bf16x3 the exact-fp32 schedules follow
     the bf16x3 ones. A call with an input prologue cannot stream (it would run the default)."""
     n = lib().pld_conv_num_schedules(math)
+    X3, PATCH, FP32, STREAM, HALO = (CONST["PLD_SCHED_" + k] for k in (
+        "X3", "X3_PATCH", "FP32", "X3_STREAM", "X3_HALO"))
     out, patch_seen = [], False
     for i in range(n):
         c = lib().pld_conv_schedule_class(math, i)
-        if c == 2 and mode == "wgrad":  # one wgrad patch schedule (it sizes its own split)
+        if c == PATCH and mode == "wgrad":  # one wgrad patch schedule (it sizes its own split)
             if patch_seen:
                 continue
             patch_seen = True
-        if mode == "wgrad" and c not in (0, 2, 3, 5):
+        if mode == "wgrad" and c not in (X3, PATCH, FP32, STREAM):
             continue
-        if c == 5 and a is not None and a.in_scale:
+        if c == STREAM and a is not None and a.in_scale:
             continue
-        if c == 2 and (a is None or not _patch_ok(mode, a)):
+        if c == PATCH and (a is None or not _patch_ok(mode, a)):
             continue
-        if c == 6 and (a is None or not _halo_ok(mode, a)
+        if c == HALO and (a is None or not _halo_ok(mode, a)
                        or ("halo28" in schedule_desc(math, i) and a.w > 28)):
             continue
         out.append(i)
@@ -406,7 +411,8 @@ def _tune(mode, a, run):
         return _TILE_CACHE[key]
     if not AUTOTUNE or _CAPTURING[0] or _skinny(a):
         return -1
-    if lib().pld_conv_kernel_kind(C.byref(a), {"fwd": 0, "dgrad": 1, "wgrad": 2}[mode]) == 2:
+    kind = lib().pld_conv_kernel_kind(C.byref(a), {"fwd": 0, "dgrad": 1, "wgrad": 2}[mode])
+    if kind == CONST["PLD_KIND_DIRECT"]:
         _TILE_CACHE[key] = -1  # direct VALU kernels (thin 1x1): no schedule to choose
         return -1
     st = torch.cuda.current_stream()
@@ -452,14 +458,6 @@ def filter_refresh(w_hwio, w_nat, w_nat_split=None, w_dg=None, w_dg_split=None):
         w_nat._pld_split = w_nat_split
     if w_dg_split is not None:
         w_dg._pld_split = w_dg_split
-
-
-class _RefreshDesc(C.Structure):
-    """Mirror of ``pld_filter_refresh_desc``."""
-    _fields_ = [("w", C.c_void_p), ("w_nat", C.c_void_p), ("w_nat_split", C.c_void_p),
-                ("w_dgrad", C.c_void_p), ("w_dgrad_split", C.c_void_p),
-                ("taps", C.c_int), ("cin", C.c_int), ("cout", C.c_int),
-                ("blk0", C.c_int), ("nblk", C.c_int), ("reserved", C.c_int)]
 
 
 class FilterRefreshBatch:
@@ -826,7 +824,8 @@ def dropconnect_scales_multi(scales, rates, layers, seed, step, image_offset=0):
                                            image_offset, stream())
 
 
-DC_MAX_LAYERS = 32  # pld_dropconnect_scales_multi rows per launch (resample.hip)
+# pld_dropconnect_scales_multi rows per launch
+DC_MAX_LAYERS = CONST["PLD_DROPCONNECT_MAX_LAYERS"]
 
 
 def bn_train_coeffs(mean, invstd, gamma, beta, scale, shift):
@@ -1080,7 +1079,7 @@ def dcg_ratio(pred, gt, ids):
 
 
 # ---- depth-edge metrics (pld_minmax_u8 / pld_*canny_u8 / pld_chamfer_dt3 / pld_depth_edge_metric)
-EDGE_MAX_DIM = 512  # PLD_EDGE_MAX_DIM: largest map side the Canny entry points take
+EDGE_MAX_DIM = CONST["PLD_EDGE_MAX_DIM"]  # largest map side the Canny entry points take
 
 
 def _u8_maps(t):
@@ -1144,9 +1143,9 @@ def depth_edge_metric(edges_op, edges_gt):
 
 
 # ---- active-learning selection (active.hip) ----
-MEDIAN_MAX_KSIZE = 15  # PLD_MEDIAN_MAX_KSIZE
-TILE_MAX = 32          # PLD_TILE_MAX: largest tile side of the tile entry points
-ORACLE_MAX_L = 16      # PLD_ORACLE_MAX_L
+MEDIAN_MAX_KSIZE = CONST["PLD_MEDIAN_MAX_KSIZE"]
+TILE_MAX = CONST["PLD_TILE_MAX"]  # largest tile side of the tile entry points
+ORACLE_MAX_L = CONST["PLD_ORACLE_MAX_L"]
 
 
 def gray(rgb):

@@ -26,6 +26,82 @@ def test_exports_are_plain_c_symbols():
         assert s in exported, s  # unmangled extern "C"
 
 
+def test_library_exports_only_declared_symbols():
+    """The header's "exports exactly the functions below": the cross-file pld__* helpers are
+    hidden, so every exported pld_* text symbol is a declared entry point."""
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
+                         text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    exported = {s for s in exported if s.startswith("pld_")}
+    assert not [s for s in exported if s.startswith("pld__")]
+    assert exported == set(_lib.declared_symbols()), exported ^ set(_lib.declared_symbols())
+
+
+P, I32, I64, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
+F32, F64, SZ = C.c_float, C.c_double, C.c_size_t
+
+
+def test_binding_parsed_from_header_matches_pinned_layouts():
+    """The structs, signatures and constants _lib reads from the header, against literals: both
+    struct layouts, prototypes that together cover every mapped type, and one enumerator of each
+    enum plus every #define."""
+    assert _lib.ConvArgs._fields_ == [
+        ("x1", P), ("x2", P), ("c1", I32), ("c2", I32),
+        ("n", I32), ("h", I32), ("w", I32),
+        ("kh", I32), ("kw", I32), ("sh", I32), ("sw", I32), ("pad_t", I32), ("pad_l", I32),
+        ("oh", I32), ("ow", I32), ("cout", I32),
+        ("in_scale", P), ("in_shift", P), ("in_act", I32), ("tile", I32),
+        ("ws", P), ("ws_bytes", SZ), ("math", I32), ("w_split", P),
+    ]
+    assert _lib.RefreshDesc._fields_ == [
+        ("w", P), ("w_nat", P), ("w_nat_split", P), ("w_dgrad", P), ("w_dgrad_split", P),
+        ("taps", I32), ("cin", I32), ("cout", I32), ("blk0", I32), ("nblk", I32),
+        ("reserved", I32),
+    ]
+    pinned = {
+        "pld_dwconv_dgrad_se_bn": (I32, [P, P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, P,
+                                         P, P, P, P, I32, P, P, P, I32, P, P, P, P, P, I32, P, P,
+                                         I32, P, P, P, SZ, P]),
+        "pld_adam_amsgrad": (I32, [P, P, P, P, P, I64, F32, F32, F32, F32, I64, F32, P]),
+        "pld_graph_end": (I32, [P, C.POINTER(P)]),
+        "pld_conv_schedule_desc": (C.c_char_p, [I32, I32]),
+        "pld_dropconnect_scales_multi": (I32, [P, I32, I32, P, P, U64, U64, P, I32, P]),
+        "pld_auto_canny_u8": (I32, [P, I32, I32, I32, F64, F64, P, P, P, P, P]),
+        "pld_conv2d_wgrad": (I32, [C.POINTER(_lib.ConvArgs), P, P, I32, P, SZ, P]),
+        "pld_conv2d_wgrad_workspace_size": (SZ, [C.POINTER(_lib.ConvArgs)]),
+    }
+    for name, sig in pinned.items():
+        assert _lib._SIGS[name] == sig, name
+    # status wrapping: by return type, and the int-valued queries by name
+    assert {"pld_conv_schedule_desc", "pld_conv2d_wgrad_workspace_size", "pld_version",
+            "pld_filter_refresh_plan"} <= _lib._NON_STATUS
+    assert not _lib._NON_STATUS & {"pld_graph_end", "pld_adam_amsgrad", "pld_conv2d_wgrad"}
+    assert len(_lib._NON_STATUS) == 28
+    for name, value in {
+            "PLD_ERR_UNSUPPORTED": 3, "PLD_ACT_SWISH": 2, "PLD_SAMPLER_INFO": 3,
+            "PLD_MATH_BF16X3": 1, "PLD_SCHED_X3_HALO": 6, "PLD_KIND_DIRECT": 2,
+            "PLD_EDGE_MAX_DIM": 512, "PLD_MEDIAN_MAX_KSIZE": 15, "PLD_TILE_MAX": 32,
+            "PLD_ORACLE_MAX_L": 16, "PLD_DROPCONNECT_MAX_LAYERS": 32}.items():
+        assert _lib.CONST[name] == value, name
+
+
+@pytest.mark.parametrize("text", [
+    "int pld_f(const foo_t* x, int n);",            # unknown type
+    "foo_t pld_f(void);",
+    "typedef struct pld_s { foo_t a; } pld_s;",
+    "int pld_f(int a, int b\nint pld_g(void);",     # unterminated prototype
+    "int pld_g(void);\nint pld_f(int a)",
+    "enum { PLD_A, PLD_B };",                       # constructs the header does not use
+    "#if 1\nint pld_f(void);\n#endif",
+    "int pld_f(int (*cb)(int));",
+])
+def test_header_parser_raises_on_what_it_does_not_understand(text):
+    assert _lib.parse_header("int pld_ok(const float* x, size_t n);")[1] == {
+        "pld_ok": (I32, [P, SZ])}
+    with pytest.raises(_lib.PLDError):
+        _lib.parse_header(text)
+
+
 def test_host_only_entry_points():
     lib = _lib.lib()
     assert lib.pld_version() == 1
