@@ -565,6 +565,24 @@ int pld_resize_nearest(const float* x, int n, int h, int w, int c, int oh, int o
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training batches from a device-resident dataset: the zip -> joint random horizontal flip ->
+ * shuffle -> batch of pldepth/data/providers/hourglass_provider.py:29-62, as one gather. For
+ * every output image b: x[b] = imgs[idx[b]], with the width axis reversed pixel-wise (the c
+ * channels of a pixel stay in order) when flip[b] != 0; gt and mask likewise with c = 1. Pure
+ * copies: the result is bit-exact.
+ *   imgs [n][h][w][c], gts / masks [n][h][w] (each NULL together with its output)
+ *   idx  [B] device int32, each in [0, n): a PRECONDITION, not checked on the device
+ *   flip [B] device int32 0/1, or NULL for no flips
+ *   x [B][h][w][c], gt / mask [B][h][w]; B * h * w <= 2^31 - 1, source offsets are 64-bit
+ * Rows of w % 4 == 0 pixels with c = 1 or 3 and 16-byte aligned bases are written as 16-byte
+ * vectors (and read as such, but for flipped c = 3 rows); any other shape is copied element by
+ * element.
+ * ------------------------------------------------------------------------------------------ */
+int pld_batch_gather_flip(const float* imgs, const float* gts, const float* masks, int n, int h,
+                          int w, int c, const int* idx, const int* flip, int B, float* x,
+                          float* gt, float* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Test-pass metrics, one workgroup per image. Pixel pairs / lists are drawn on
  * the host exactly as the reference draws them and passed as int32 flat pixel indices.
  * ------------------------------------------------------------------------------------------ */

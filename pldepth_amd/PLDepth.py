@@ -7,6 +7,8 @@ Differences from the reference driver, all outside the accelerated path (SURVEY 
   * data: ``--hr_wsi_path`` reads the HR-WSI tree (pldepth_amd.data.dao.hr_wsi: host decode, GPU
     resize); ``--data_npz`` loads in-memory arrays (imgs [N,H,W,3] in [0,1], gts [N,H,W],
     masks [N,H,W]); without either a seeded synthetic HR-WSI-shaped set is generated;
+  * ``--device_data true`` uploads the train and val sets once and assembles every batch on the
+    GPU (``pld_batch_gather_flip``) instead of on the host;
   * no wandb / mlflow: metrics go to stdout and ``--log_jsonl``;
   * ``--input_size`` (the reference hard-codes 224 here and 448 in run_scripts/test_sampling.py).
 Everything per step — sampling, forward, ListMLE, backward, Adam-AMSGrad — runs on the GPU.
@@ -87,11 +89,14 @@ class JSONLLogger(object):
 @click.option('--save_path', default='', help='save weights after training (.h5: Keras HDF5, '
               'else .npz) and the whole model as <stem>_model.h5')
 @click.option('--log_jsonl', default='', help='per-batch metrics file')
+@click.option('--device_data', default=False, type=click.BOOL,
+              help='keep the train and val sets in device memory and gather each batch there '
+              '(same batches as the host path)')
 def perform_pldepth_experiment(model_name, epochs, batch_size, seed, ranking_size,
                                rankings_per_image, initial_lr, equality_threshold,
                                model_checkpoints, load_model_path, augmentation, warmup,
                                sampling_type, lr_multi, ds_size, input_size, data_npz, save_path,
-                               log_jsonl, hr_wsi_path=''):
+                               log_jsonl, hr_wsi_path='', device_data=False):
     np.random.seed(seed)
     model_params = ModelParameters()
     model_params.set_parameter("model_type", get_model_type_by_name(model_name))
@@ -148,7 +153,8 @@ def perform_pldepth_experiment(model_name, epochs, batch_size, seed, ranking_siz
     if load_model_path:
         model.load_weights(load_model_path)
     provider = HourglassLargeScaleDataProvider(model_params, masks[n_val:], masks[:n_val],
-                                               augmentation=augmentation, seed=seed)
+                                               augmentation=augmentation, seed=seed,
+                                               device_resident=device_data)
     train_ds = provider.provide_train_dataset(preprocess_fn(imgs[n_val:]), gts[n_val:])
     val_ds = (provider.provide_val_dataset(preprocess_fn(imgs[:n_val]), gts[:n_val])
               if n_val >= batch_size else None)

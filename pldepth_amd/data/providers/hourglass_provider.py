@@ -9,17 +9,52 @@ Here the datasets are in-memory arrays (images [N,H,W,3] in [0,1], gts [N,H,W], 
 flips and shuffling are host index work, and the rankings of a whole batch come from ONE GPU
 sampler launch (Philox draws keyed by seed / batch counter / image position) instead of a
 per-image Python call under the GIL. Batches are (x [B,H,W,3], y [B,R,L,2]) device tensors.
+
+With ``device_resident=True`` the arrays are uploaded once and the gather and flip of a batch are
+one kernel as well (pld_batch_gather_flip); the host keeps only the index work.
 """
 import numpy as np
 import torch
 
+from ... import kernels as K
 from ..sampling import ThresholdedMaskedRandomSamplingStrategy
 
 
+UPLOAD_CHUNK = 256  # images per host-to-device copy of a resident dataset
+
+
+def _resident(arrays, dev):
+    """float32 device copies of the host arrays, uploaded UPLOAD_CHUNK images at a time so the
+    host never holds a second full-size (converted / contiguous) copy. All or nothing: when the
+    device runs out of memory what was uploaded is freed and MemoryError raised."""
+    need = sum(int(np.prod(a.shape)) * 4 for a in arrays)
+    out = []
+    try:
+        for a in arrays:
+            t = torch.empty(tuple(a.shape), dtype=torch.float32, device=dev)
+            out.append(t)
+            for i in range(0, len(a), UPLOAD_CHUNK):
+                t[i:i + UPLOAD_CHUNK].copy_(torch.from_numpy(
+                    np.ascontiguousarray(a[i:i + UPLOAD_CHUNK], np.float32)))
+    except torch.cuda.OutOfMemoryError:
+        del out[:]
+        t = None
+        torch.cuda.empty_cache()
+        raise MemoryError(
+            f"device_resident=True needs {need} bytes of device memory for the dataset and "
+            f"{torch.cuda.mem_get_info(dev)[0]} are free; device_resident=False keeps the "
+            "dataset on the host") from None
+    return out
+
+
 class HourglassLargeScaleDataProvider(object):
+    """``device_resident=True``: the datasets are uploaded once, when provide_*_dataset is
+    called, and every training batch is gathered (and flipped) on the device by
+    kernels.batch_gather_flip: the same batches, bit for bit, as the host path for a seed."""
+
     def __init__(self, model_params, train_consistency_masks, val_consistency_masks,
                  loss_type=None, augmentation=False, sampling_eq_threshold=0.03, bs_factor=5,
-                 seed=0):
+                 seed=0, device_resident=False):
         self.model_params = model_params
         self.train_consistency_masks = np.asarray(train_consistency_masks, np.float32)
         self.val_consistency_masks = (None if val_consistency_masks is None else
@@ -31,18 +66,33 @@ class HourglassLargeScaleDataProvider(object):
         self.loss_type = loss_type
         self.bs_factor = bs_factor
         self.seed = seed
+        self.device_resident = device_resident
 
     def provide_train_dataset(self, base_ds, base_ds_gts=None):
+        if self.device_resident:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            return _ResidentTrainIterable(self, *_resident(
+                [np.asarray(base_ds), np.asarray(base_ds_gts), self.train_consistency_masks], dev))
         return _TrainIterable(self, np.asarray(base_ds, np.float32),
                               np.asarray(base_ds_gts, np.float32))
 
     def provide_val_dataset(self, base_ds, base_ds_gts=None):
-        imgs = np.asarray(base_ds, np.float32)
-        gts = np.asarray(base_ds_gts, np.float32)
         B = self.model_params.get_parameter("batch_size")
         R = self.model_params.get_parameter("val_rankings_per_img")
         dev = torch.device("cuda", torch.cuda.current_device())
         batches = []
+        if self.device_resident:  # one upload of the full batches; x is a slice of it
+            n = len(base_ds) // B * B
+            imgs, gts, masks = _resident([np.asarray(base_ds)[:n], np.asarray(base_ds_gts)[:n],
+                                          self.val_consistency_masks[:n]], dev)
+            for i in range(0, n, B):
+                y = self.val_random_sampler.sample_batch_gpu(
+                    gts[i:i + B], masks[i:i + B], R, seed=self.seed + 7919, step=0,
+                    image_offset=i)
+                batches.append((imgs[i:i + B], y))
+            return batches
+        imgs = np.asarray(base_ds, np.float32)
+        gts = np.asarray(base_ds_gts, np.float32)
         for i in range(0, len(imgs) - B + 1, B):  # batch(drop_remainder=True) + cache()
             y = self.val_random_sampler.sample_batch_gpu(
                 torch.from_numpy(gts[i:i + B]).to(dev),
@@ -50,6 +100,32 @@ class HourglassLargeScaleDataProvider(object):
                 seed=self.seed + 7919, step=0, image_offset=i)
             batches.append((torch.from_numpy(imgs[i:i + B]).to(dev), y))
         return batches
+
+
+class _ResidentTrainIterable(object):
+    """_TrainIterable over device tensors: the same host RNG stream (one permutation per epoch,
+    one flip draw per batch) and sampler step counter, the batch from one gather kernel."""
+
+    def __init__(self, prov, imgs, gts, masks):
+        self.p, self.imgs, self.gts, self.masks = prov, imgs, gts, masks
+
+    def __iter__(self):
+        p = self.p
+        B = p.model_params.get_parameter("batch_size")
+        R = p.model_params.get_parameter("rankings_per_image")
+        strategy = p.model_params.get_parameter("sampling_strategy") or p.random_sampler
+        rng = np.random.default_rng(p.seed)
+        n = len(self.imgs)
+        step = 0
+        while True:  # repeat()
+            order = rng.permutation(n)
+            for i in range(0, n - B + 1, B):
+                flip = rng.random(B) > 0.5 if p.augmentation else None
+                x, g, m = K.batch_gather_flip(self.imgs, self.gts, self.masks, order[i:i + B],
+                                              flip)
+                y = strategy.sample_batch_gpu(g, m, R, seed=p.seed, step=step, image_offset=0)
+                step += 1
+                yield x, y
 
 
 class _TrainIterable(object):

@@ -1221,3 +1221,46 @@ def resize(x, oh, ow, method="bilinear", out=None):
     fn = lib().pld_resize_bilinear if method == "bilinear" else lib().pld_resize_nearest
     fn(ptr(_f32(x.contiguous())), n, h, w, c, oh, ow, ptr(out), stream())
     return out
+
+
+# ---- device-resident training batches (pld_batch_gather_flip) ----
+def batch_gather_flip(imgs, gts, masks, idx, flip, out=None):
+    """imgs [n, h, w, c], gts / masks [n, h, w] (or None) float32 device tensors; idx: B host
+    integers in [0, n); flip: B host 0/1 values or None -> (x [B, h, w, c], gt, mask [B, h, w]):
+    x[b] = imgs[idx[b]], mirrored left-right where flip[b] (gt and mask with it; None where the
+    source is None). ``out``: the (x, gt, mask) tensors to fill instead of fresh ones."""
+    n, h, w, c = imgs.shape
+    idx = np.asarray(idx)
+    if idx.ndim != 1 or idx.size == 0 or idx.dtype.kind not in "iu":
+        raise ValueError(f"batch_gather_flip: idx must be a non-empty 1-d integer array, "
+                         f"got {idx.dtype} {idx.shape}")
+    if idx.min() < 0 or idx.max() >= n:  # the kernel does not check: see pld_batch_gather_flip
+        bad = int(idx.min() if idx.min() < 0 else idx.max())
+        raise ValueError(f"batch_gather_flip: index {bad} outside a dataset of {n} images")
+    B = idx.size
+    sel = np.zeros((2, B), np.int32)  # one upload: indices, then flips
+    sel[0] = idx
+    if flip is not None:
+        flip = np.asarray(flip)
+        if flip.shape != (B,):
+            raise ValueError(f"batch_gather_flip: flip has shape {flip.shape}, idx {idx.shape}")
+        sel[1] = flip != 0
+    for t in (gts, masks):
+        assert t is None or tuple(t.shape) == (n, h, w), (tuple(t.shape), (n, h, w))
+    dev = imgs.device
+    if out is None:
+        x = torch.empty((B, h, w, c), dtype=torch.float32, device=dev)
+        gt = None if gts is None else torch.empty((B, h, w), dtype=torch.float32, device=dev)
+        mask = None if masks is None else torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    else:
+        x, gt, mask = out
+        assert tuple(x.shape) == (B, h, w, c) and (gt is None) == (gts is None) \
+            and (mask is None) == (masks is None)
+        assert all(t is None or tuple(t.shape) == (B, h, w) for t in (gt, mask))
+    sel_d = torch.from_numpy(sel).to(dev)
+    lib().pld_batch_gather_flip(
+        ptr(_f32(imgs)), ptr(None if gts is None else _f32(gts)),
+        ptr(None if masks is None else _f32(masks)), n, h, w, c, ptr(sel_d[0]),
+        None if flip is None else ptr(sel_d[1]), B, ptr(_f32(x)),
+        ptr(None if gt is None else _f32(gt)), ptr(None if mask is None else _f32(mask)), stream())
+    return x, gt, mask
