@@ -10,11 +10,16 @@ Differences from the reference driver, all outside the accelerated path (SURVEY 
   * ``--device_data true`` uploads the train and val sets once and assembles every batch on the
     GPU (``pld_batch_gather_flip``) instead of on the host;
   * no wandb / mlflow: metrics go to stdout and ``--log_jsonl``;
-  * ``--input_size`` (the reference hard-codes 224 here and 448 in run_scripts/test_sampling.py).
+  * ``--input_size`` (the reference hard-codes 224 here and 448 in run_scripts/test_sampling.py);
+  * ``--gpus N``: data-parallel training, one process per GPU (``--batch_size`` stays the per-GPU
+    batch). Started without a launcher, the command runs its N ranks as one
+    ``torch.distributed.run`` child and returns that child's exit code; rank 0 prints, logs,
+    saves and runs the test pass.
 Everything per step — sampling, forward, ListMLE, backward, Adam-AMSGrad — runs on the GPU.
 """
 import json
 import os
+import sys
 import time
 
 import click
@@ -30,6 +35,7 @@ from .data.sampling import (InformationScoreBasedSampling, PurelyMaskedRandomSam
 from .data.providers.hourglass_provider import HourglassLargeScaleDataProvider
 from .util.training_utils import LearningRateLoggingCallback, SGDRScheduler, TerminateOnNaN
 from .active_learning.metrics import calc_err, dcg_metric
+from . import dp
 
 
 def synthetic_hrwsi(n, h, w, seed=0):
@@ -60,10 +66,21 @@ class JSONLLogger(object):
         self.model = model
 
     def on_batch_end(self, batch, logs=None):
-        if self.path:
+        if self.path and getattr(self.model, "rank", 0) == 0:  # data parallel: rank 0 writes
             with open(self.path, "a") as f:
                 f.write(json.dumps({"t": time.time() - self.t0, "batch": batch,
                                     "lr": self.model.optimizer.lr, **(logs or {})}) + "\n")
+
+
+def steps_per_epoch_for(ds_size, batch_size, world=1):
+    """PLDepth.py:120 with the global batch: 14/15 of the set trains, batch_size * world images
+    per step."""
+    return max(1, int((ds_size * 14 / 15) / (batch_size * world)))
+
+
+def _argv(params):
+    """The command line that parses back to `params` (every option is `--name value`)."""
+    return [a for k, v in params.items() if v is not None for a in (f"--{k}", str(v))]
 
 
 @click.command()
@@ -92,11 +109,45 @@ class JSONLLogger(object):
 @click.option('--device_data', default=False, type=click.BOOL,
               help='keep the train and val sets in device memory and gather each batch there '
               '(same batches as the host path)')
-def perform_pldepth_experiment(model_name, epochs, batch_size, seed, ranking_size,
-                               rankings_per_image, initial_lr, equality_threshold,
-                               model_checkpoints, load_model_path, augmentation, warmup,
-                               sampling_type, lr_multi, ds_size, input_size, data_npz, save_path,
-                               log_jsonl, hr_wsi_path='', device_data=False):
+@click.option('--gpus', default=None, type=click.INT,
+              help='data-parallel ranks, one process per GPU; --batch_size is per GPU '
+              '(default: WORLD_SIZE under a launcher, else 1)')
+@click.option('--dist_backend', default=None, type=click.Choice(['nccl', 'gloo']),
+              help='torch.distributed backend for --gpus > 1 (default: PLD_DP_BACKEND, else nccl '
+              '= RCCL; gloo lets the ranks share GPUs)')
+def perform_pldepth_experiment(gpus=None, dist_backend=None, **params):
+    if gpus is None:  # under torch.distributed.run the launcher has said how many
+        gpus = int(os.environ.get("WORLD_SIZE", "1"))
+    if gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # no launcher: the ranks run in ONE fresh child; this process never opens the GPU
+        argv = _argv(dict(params, gpus=gpus, dist_backend=dist_backend))
+        sys.exit(dp.spawn_ranks(gpus, argv, module="pldepth_amd.PLDepth"))
+    rank, world, local_rank = dp.env_rank_world()
+    if world != gpus:
+        raise click.UsageError(f"--gpus {gpus} but WORLD_SIZE={world}")
+    if world == 1:
+        return run_experiment(**params)
+
+    def rank_main():
+        import torch
+        import torch.distributed as dist
+        dev = local_rank % max(torch.cuda.device_count(), 1)  # ranks beyond the GPUs share them
+        torch.cuda.set_device(dev)
+        dp.init_group(dist_backend or os.environ.get("PLD_DP_BACKEND", "nccl"), rank, world,
+                      device=torch.device("cuda", dev),
+                      timeout_s=float(os.environ.get("PLD_DP_TIMEOUT", "600")))
+        code = run_experiment(rank=rank, world=world, **params)
+        dist.destroy_process_group()
+        return code
+    return dp.exit_on_failure(rank_main, world)
+
+
+def run_experiment(model_name, epochs, batch_size, seed, ranking_size, rankings_per_image,
+                   initial_lr, equality_threshold, model_checkpoints, load_model_path,
+                   augmentation, warmup, sampling_type, lr_multi, ds_size, input_size, data_npz,
+                   save_path, log_jsonl, hr_wsi_path='', device_data=False, rank=0, world=1):
+    """One rank's run (world 1: the whole run). With world > 1 the default process group is
+    initialised: compile() makes the model a data-parallel replica of it."""
     np.random.seed(seed)
     model_params = ModelParameters()
     model_params.set_parameter("model_type", get_model_type_by_name(model_name))
@@ -144,7 +195,7 @@ def perform_pldepth_experiment(model_name, epochs, batch_size, seed, ranking_siz
         eval_imgs, eval_gts, _ = synthetic_hrwsi(n_eval, input_size, input_size, seed + 1)
     ds_size = len(imgs)
     n_val = ds_size // 15
-    steps_per_epoch = max(1, int((ds_size * 14 / 15) / batch_size))  # PLDepth.py:120
+    steps_per_epoch = steps_per_epoch_for(ds_size, batch_size, world)
     schedule = SGDRScheduler(min_lr=initial_lr * (1 / lr_multi), max_lr=initial_lr,
                              steps_per_epoch=steps_per_epoch, lr_decay=0.9, cycle_length=epochs,
                              mult_factor=1)
@@ -154,10 +205,11 @@ def perform_pldepth_experiment(model_name, epochs, batch_size, seed, ranking_siz
         model.load_weights(load_model_path)
     provider = HourglassLargeScaleDataProvider(model_params, masks[n_val:], masks[:n_val],
                                                augmentation=augmentation, seed=seed,
+                                               rank=rank, world=world,
                                                device_resident=device_data)
     train_ds = provider.provide_train_dataset(preprocess_fn(imgs[n_val:]), gts[n_val:])
     val_ds = (provider.provide_val_dataset(preprocess_fn(imgs[:n_val]), gts[:n_val])
-              if n_val >= batch_size else None)
+              if n_val >= batch_size * world else None)
     callbacks = [TerminateOnNaN(), schedule, LearningRateLoggingCallback(), JSONLLogger(log_jsonl)]
     if model_checkpoints:  # tracking_utils.py:21-30 (best val_loss -> Keras .h5 model file)
         from .util.env import get_config
@@ -165,9 +217,17 @@ def perform_pldepth_experiment(model_name, epochs, batch_size, seed, ranking_siz
         callbacks.append(construct_model_checkpoint_callback(get_config(), model_name, 1))
     model.fit(x=train_ds, epochs=epochs, steps_per_epoch=steps_per_epoch, callbacks=callbacks,
               validation_data=val_ds, verbose=1)
-    if save_path:  # PLDepth.py:180-181: weights, plus the whole model as .h5
+    # fit left every replica with the same weights and BN statistics: rank 0 alone saves and
+    # runs the test pass. The others wait in a barrier for the save only, so the test pass,
+    # however long, is not bounded by the collectives' timeout
+    if save_path and rank == 0:  # PLDepth.py:180-181: weights, plus the whole model as .h5
         model.save_weights(save_path)
         model.save(os.path.splitext(save_path)[0] + "_model.h5")
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        if rank != 0:
+            return 0
     # test pass (PLDepth.py:183-192): ordinal error and nDCG@200 on the first 250 images of the
     # held-out eval split, on the GPU (pldepth_amd.active_learning.metrics). Like the reference,
     # the images go in raw (no preprocess_fn: PLDepth.py:187-191 calls calc_err / dcg_metric on

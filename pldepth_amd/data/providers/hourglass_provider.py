@@ -12,6 +12,12 @@ per-image Python call under the GIL. Batches are (x [B,H,W,3], y [B,R,L,2]) devi
 
 With ``device_resident=True`` the arrays are uploaded once and the gather and flip of a batch are
 one kernel as well (pld_batch_gather_flip); the host keeps only the index work.
+
+Data parallel (``rank``, ``world``): ``batch_size`` stays the per-replica batch B and the global
+batch is G = world * B. Every rank holds the whole dataset and runs the same host RNG stream; rank
+r takes images [r*B, (r+1)*B) of each global batch (dp.shard's layout) and samples them with
+``image_offset = r*B``, so its (x, y) are, bit for bit, that slice of what one process with batch
+G produces.
 """
 import numpy as np
 import torch
@@ -47,6 +53,19 @@ def _resident(arrays, dev):
     return out
 
 
+def _epoch_batches(rng, n, B, world=1, rank=0, augment=False):
+    """One epoch's index work: yields (idx [B], flip [B] bool or None) per global batch, rank
+    ``rank``'s slice of it. The draws from ``rng`` do not depend on the rank: one permutation of
+    the n images, then per global batch of G = world * B one flip draw of G when augmenting
+    (drop_remainder: the last n % G images of the permutation are not used)."""
+    G = world * B
+    lo = rank * B
+    order = rng.permutation(n)
+    for i in range(0, n - G + 1, G):
+        flip = rng.random(G) > 0.5 if augment else None
+        yield order[i + lo:i + lo + B], None if flip is None else flip[lo:lo + B]
+
+
 class HourglassLargeScaleDataProvider(object):
     """``device_resident=True``: the datasets are uploaded once, when provide_*_dataset is
     called, and every training batch is gathered (and flipped) on the device by
@@ -54,7 +73,9 @@ class HourglassLargeScaleDataProvider(object):
 
     def __init__(self, model_params, train_consistency_masks, val_consistency_masks,
                  loss_type=None, augmentation=False, sampling_eq_threshold=0.03, bs_factor=5,
-                 seed=0, device_resident=False):
+                 seed=0, rank=0, world=1, device_resident=False):
+        if not 0 <= rank < world:
+            raise ValueError(f"rank {rank} outside a world of {world}")
         self.model_params = model_params
         self.train_consistency_masks = np.asarray(train_consistency_masks, np.float32)
         self.val_consistency_masks = (None if val_consistency_masks is None else
@@ -66,6 +87,7 @@ class HourglassLargeScaleDataProvider(object):
         self.loss_type = loss_type
         self.bs_factor = bs_factor
         self.seed = seed
+        self.rank, self.world = rank, world
         self.device_resident = device_resident
 
     def provide_train_dataset(self, base_ds, base_ds_gts=None):
@@ -79,13 +101,14 @@ class HourglassLargeScaleDataProvider(object):
     def provide_val_dataset(self, base_ds, base_ds_gts=None):
         B = self.model_params.get_parameter("batch_size")
         R = self.model_params.get_parameter("val_rankings_per_img")
+        G, lo = self.world * B, self.rank * B  # global batches of G; this rank's B of each
         dev = torch.device("cuda", torch.cuda.current_device())
         batches = []
         if self.device_resident:  # one upload of the full batches; x is a slice of it
-            n = len(base_ds) // B * B
+            n = len(base_ds) // G * G
             imgs, gts, masks = _resident([np.asarray(base_ds)[:n], np.asarray(base_ds_gts)[:n],
                                           self.val_consistency_masks[:n]], dev)
-            for i in range(0, n, B):
+            for i in range(lo, n, G):
                 y = self.val_random_sampler.sample_batch_gpu(
                     gts[i:i + B], masks[i:i + B], R, seed=self.seed + 7919, step=0,
                     image_offset=i)
@@ -93,7 +116,7 @@ class HourglassLargeScaleDataProvider(object):
             return batches
         imgs = np.asarray(base_ds, np.float32)
         gts = np.asarray(base_ds_gts, np.float32)
-        for i in range(0, len(imgs) - B + 1, B):  # batch(drop_remainder=True) + cache()
+        for i in range(lo, len(imgs) - G + lo + 1, G):  # batch(drop_remainder=True) + cache()
             y = self.val_random_sampler.sample_batch_gpu(
                 torch.from_numpy(gts[i:i + B]).to(dev),
                 torch.from_numpy(self.val_consistency_masks[i:i + B]).to(dev), R,
@@ -118,12 +141,10 @@ class _ResidentTrainIterable(object):
         n = len(self.imgs)
         step = 0
         while True:  # repeat()
-            order = rng.permutation(n)
-            for i in range(0, n - B + 1, B):
-                flip = rng.random(B) > 0.5 if p.augmentation else None
-                x, g, m = K.batch_gather_flip(self.imgs, self.gts, self.masks, order[i:i + B],
-                                              flip)
-                y = strategy.sample_batch_gpu(g, m, R, seed=p.seed, step=step, image_offset=0)
+            for idx, flip in _epoch_batches(rng, n, B, p.world, p.rank, p.augmentation):
+                x, g, m = K.batch_gather_flip(self.imgs, self.gts, self.masks, idx, flip)
+                y = strategy.sample_batch_gpu(g, m, R, seed=p.seed, step=step,
+                                              image_offset=p.rank * B)
                 step += 1
                 yield x, y
 
@@ -143,17 +164,15 @@ class _TrainIterable(object):
         n = len(self.imgs)
         step = 0
         while True:  # repeat()
-            order = rng.permutation(n)
-            for i in range(0, n - B + 1, B):
-                idx = order[i:i + B]
+            for idx, flip in _epoch_batches(rng, n, B, p.world, p.rank, p.augmentation):
                 x, g, m = self.imgs[idx], self.gts[idx], self.masks[idx]
-                if p.augmentation:  # joint random horizontal flip, p = 0.5 (:35-49)
-                    flip = rng.random(B) > 0.5
+                if flip is not None:  # joint random horizontal flip, p = 0.5 (:35-49)
                     x = np.where(flip[:, None, None, None], x[:, :, ::-1], x)
                     g = np.where(flip[:, None, None], g[:, :, ::-1], g)
                     m = np.where(flip[:, None, None], m[:, :, ::-1], m)
                 gd = torch.from_numpy(np.ascontiguousarray(g)).to(dev)
                 md = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
-                y = strategy.sample_batch_gpu(gd, md, R, seed=p.seed, step=step, image_offset=0)
+                y = strategy.sample_batch_gpu(gd, md, R, seed=p.seed, step=step,
+                                              image_offset=p.rank * B)
                 step += 1
                 yield torch.from_numpy(np.ascontiguousarray(x)).to(dev), y

@@ -107,6 +107,40 @@ def replicas_identical(buf, group=None):
     return lo == hi, {"min": lo, "max": hi}
 
 
+def allreduce_mean(t, world, group=None):
+    """In place: the mean over the group's ranks of tensor `t` (sum-all-reduce, then x 1/world),
+    ordered after the caller's current stream. Not for the step's gradient (Adam folds that
+    1/world in): the per-step loss scalar, the per-epoch BN moving statistics, val_loss. A
+    non-finite element on any rank comes out non-finite on every rank."""
+    import torch.distributed as dist
+    dist.all_reduce(t, group=group)
+    return t.mul_(1.0 / world)
+
+
+def _free_port():
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def spawn_ranks(n, argv, module):
+    """Run `n` ranks of `python -m module argv...` on this host as ONE fresh child process,
+    `torch.distributed.run --nproc-per-node n` on 127.0.0.1 with a free port (each rank finds
+    RANK / WORLD_SIZE / LOCAL_RANK in its environment), and return the child's exit code. For a
+    parent that has not touched the GPU: it only waits."""
+    import subprocess
+    import sys
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+           "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), "-m", module] + list(argv)
+    env = dict(os.environ)
+    env.setdefault("OMP_NUM_THREADS", "4")
+    return subprocess.call(cmd, env=env)
+
+
 def exit_on_failure(fn, world):
     """Run fn(); in a multi-rank job an exception (a dead peer, a collective past its timeout)
     ends THIS rank at once with a non-zero status instead of leaving it blocked in a later
@@ -127,4 +161,5 @@ def exit_on_failure(fn, world):
 
 
 __all__ = ["env_rank_world", "shard", "tensor_buckets", "allreduce_bucket", "init_group",
-           "rccl_version", "replica_checksum", "replicas_identical", "exit_on_failure"]
+           "rccl_version", "replica_checksum", "replicas_identical", "allreduce_mean",
+           "spawn_ranks", "exit_on_failure"]

@@ -15,6 +15,7 @@ identity (its Rescaling/Normalization live inside the model).
 import abc
 import logging
 import math
+import os
 
 import numpy as np
 import torch
@@ -39,6 +40,7 @@ class FullyFledgedModel(object):
         self.trainer = None
         self.stop_training = False
         self.history = {}
+        self.rank, self.world, self.distributed = 0, 1, False  # compile(distribute=...)
 
     # ------------------------------------------------------------------ properties
     @property
@@ -57,16 +59,50 @@ class FullyFledgedModel(object):
         pass
 
     # ------------------------------------------------------------------ compile / train
-    def compile(self, loss=None, optimizer=None, **kwargs):
+    def compile(self, loss=None, optimizer=None, distribute=None, **kwargs):
+        """``distribute``: None takes (rank, world) from the launcher's environment
+        (dp.env_rank_world: RANK / WORLD_SIZE), or an explicit ``(rank, world, process_group)``.
+        With world > 1, or a group given, this model is one data-parallel replica: the trainer
+        exchanges the gradient over the group (the initialised default group, else one created
+        here: backend PLD_DP_BACKEND, default nccl = RCCL), and every rank must hold the same
+        parameters and frozen weights (same seed or same weights file; checked, not broadcast).
+        A group given at world 1 keeps the trainer's single-graph step (it has nothing to
+        exchange); the loss and statistics collectives then run over that one rank."""
+        from .. import dp
         from ..optimizers import Adam
         from ..trainer import ReplicaTrainer
         self.loss = loss
         self.optimizer = optimizer if optimizer is not None else Adam(amsgrad=True)
         eng = self.engine
+        if distribute is None:
+            distribute = dp.env_rank_world()[:2] + (None,)
+        rank, world, pg = distribute
+        if not 0 <= rank < world:
+            raise ValueError(f"rank {rank} outside a world of {world}")
+        self.rank, self.world = rank, world
+        self.distributed = world > 1 or pg is not None
+        dist_kw = {}
+        if self.distributed:
+            import torch.distributed as dist
+            if pg is None:
+                if not dist.is_initialized():
+                    # bounded: a rank that dies or never arrives ends the job, not a hang
+                    dp.init_group(os.environ.get("PLD_DP_BACKEND", "nccl"), rank, world,
+                                  device=torch.device("cuda", torch.cuda.current_device()),
+                                  timeout_s=float(os.environ.get("PLD_DP_TIMEOUT", "600")))
+                pg = dist.group.WORLD
+            if dist.get_world_size(pg) != world:
+                raise ValueError(f"world {world} but the process group has "
+                                 f"{dist.get_world_size(pg)} ranks")
+            dist_kw = dict(rank=rank, world_size=world, process_group=pg)
+            # the mean-loss scalar all-reduced after each step (outside the captured graphs)
+            self._loss_mean = torch.zeros(1, device=eng.device)
         self.trainer = ReplicaTrainer((eng.H, eng.W, 3), eng.B, loss.ranking_size, 1,
                                       engine=eng, gpu_sampler=False,
                                       beta_1=self.optimizer.beta_1, beta_2=self.optimizer.beta_2,
-                                      epsilon=self.optimizer.epsilon)
+                                      epsilon=self.optimizer.epsilon, **dist_kw)
+        if self.distributed:
+            self._check_replicas()
         self._captured = False
         pending = getattr(self, "_pending_optimizer_state", None)
         if pending:  # a load_model()ed file: restore its Adam slots now that they exist
@@ -93,12 +129,55 @@ class FullyFledgedModel(object):
         else:
             tr.step(self.optimizer.lr)
         self.optimizer.iterations += 1
-        return tr.loss_value() if return_loss else None
+        if not return_loss:
+            return None
+        return self._mean_loss() if self.distributed else tr.loss_value()
+
+    def _mean_loss(self):
+        """The global batch's loss: the mean over ranks of the replicas' losses, one 1-element
+        all-reduce issued behind the step's exchange (between graph launches, like the bucket
+        all-reduces), then the readback. Non-finite on one rank is non-finite on all, so
+        TerminateOnNaN / stop_training agree everywhere."""
+        from .. import dp
+        tr = self.trainer
+        with torch.cuda.stream(tr.stream):
+            self._loss_mean.copy_(tr.loss)
+            dp.allreduce_mean(self._loss_mean, self.world, tr.pg)
+        torch.cuda.current_stream().wait_stream(tr.stream)
+        return float(self._loss_mean.item())
+
+    def sync_moving_stats(self):
+        """Data parallel: replace every replica's BN moving statistics by their mean over the
+        ranks (sum-all-reduce of the engine's flat statistics buffer, x 1/world, in place), so
+        the inference-mode forward (evaluate, predict) and saved weights are the same on every
+        rank. Per-epoch work (fit calls it at each epoch's end); nothing of it is in the step. A
+        single replica: nothing to do."""
+        if not self.distributed:
+            return
+        from .. import dp
+        tr = self.trainer
+        tr._order_after_caller()  # e.g. a set_weights on the caller's stream
+        with torch.cuda.stream(tr.stream):
+            dp.allreduce_mean(self.engine.stats.buf, self.world, tr.pg)
+        torch.cuda.current_stream().wait_stream(tr.stream)
+
+    def _check_replicas(self):
+        """Every rank holds the same parameters and frozen weights, bit for bit, or raise."""
+        from .. import dp
+        torch.cuda.synchronize()
+        for what in ("params", "frozen"):
+            same, sums = dp.replicas_identical(getattr(self.engine, what).buf, self.trainer.pg)
+            if not same:
+                raise RuntimeError(
+                    f"data-parallel replicas differ in their {what} (checksums {sums}): build "
+                    "every rank's model from the same seed or load the same weights file")
 
     def fit(self, x=None, y=None, epochs=1, steps_per_epoch=None, callbacks=None,
             validation_data=None, verbose=1, initial_epoch=0, **kwargs):
         """Keras-style loop. ``x``: an iterable of (x_batch, y_batch) pairs (a provider dataset,
-        repeated as needed), or an array with ``y`` given."""
+        repeated as needed), or an array with ``y`` given. Data parallel: the iterable yields
+        this rank's shard of each global batch (the provider's ``rank=`` / ``world=``); arrays
+        are refused at world > 1, since nothing would shard them."""
         callbacks = list(callbacks or [])
         for cb in callbacks:
             if hasattr(cb, "set_model"):
@@ -106,6 +185,10 @@ class FullyFledgedModel(object):
             else:
                 cb.model = self
         if x is not None and y is not None:
+            if self.world > 1:
+                raise ValueError("fit(x=array, y=array) on a data-parallel replica: every rank "
+                                 "would train on the same batches; pass this rank's shard as an "
+                                 "iterable of (x, y) batches")
             xs, ys = np.asarray(x), np.asarray(y)
             B = self.batch_size
             n = len(xs) // B
@@ -140,16 +223,20 @@ class FullyFledgedModel(object):
                 if self.stop_training:
                     break
             logs = {"loss": float(np.mean(losses)) if losses else float("nan")}
+            # before evaluate and on_epoch_end: validation and a checkpoint callback see the
+            # reconciled BN moving statistics
+            self.sync_moving_stats()
             if validation_data is not None:
                 logs["val_loss"] = self.evaluate(validation_data, verbose=0)
             for k, v in logs.items():
                 self.history.setdefault(k, []).append(v)
-            if verbose:
+            if verbose and self.rank == 0:
                 print(f"Epoch {epoch + 1}/{epochs} - " +
                       " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()), flush=True)
             self._cb("on_epoch_end", callbacks, epoch, logs)
             if self.stop_training:
                 break
+        self.sync_moving_stats()
         self._cb("on_train_end", callbacks)
         return self
 
@@ -193,12 +280,20 @@ class FullyFledgedModel(object):
         return np.concatenate(outs) if outs else np.zeros((0, self.engine.H, self.engine.W, 1))
 
     def evaluate(self, data, verbose=0):
-        """Mean loss over (x, y) batches with BN in inference mode (Keras validation)."""
+        """Mean loss over (x, y) batches with BN in inference mode (Keras validation). Data
+        parallel: ``data`` is this rank's shard of every global batch (the provider's val
+        dataset); the result is the mean over ranks, exact since the shards hold equally many
+        lists."""
         losses = []
         for xb, yb in data:
             pred = self(xb, training=False)
             losses.append(float(self.loss(yb, pred).item()))
-        return float(np.mean(losses)) if losses else float("nan")
+        mean = float(np.mean(losses)) if losses else float("nan")
+        if self.distributed:
+            from .. import dp
+            t = torch.tensor([mean], dtype=torch.float64, device=self.trainer.device)
+            mean = float(dp.allreduce_mean(t, self.world, self.trainer.pg).item())
+        return mean
 
     # ------------------------------------------------------------------ weights
     def get_weights(self):
@@ -229,7 +324,10 @@ class FullyFledgedModel(object):
         from ..util import hdf5
         if hdf5.is_hdf5(path):
             from ..util import keras_h5
-            return keras_h5.load_weights(self.engine, path)
+            res = keras_h5.load_weights(self.engine, path)
+            if self.distributed:
+                self._check_replicas()
+            return res
         path = path if path.endswith(".npz") else path + ".npz"
         with np.load(path, allow_pickle=False) as z:
             w = {k: z[k] for k in z.files}
@@ -239,6 +337,8 @@ class FullyFledgedModel(object):
             for store, name in ((m, "m"), (v, "v"), (vh, "vhat")):
                 store.copy_(torch.from_numpy(w[f"__adam__/{name}"]))
             self.trainer.step_dev.copy_(torch.from_numpy(w["__adam__/step"]))
+        if self.distributed:
+            self._check_replicas()
 
     def save(self, filepath, overwrite=True, include_optimizer=True, **kwargs):
         """keras.Model.save('... .h5') (PLDepth.py:181): model config, weights and the Adam

@@ -134,6 +134,8 @@ class ModelCheckpoint(Callback):
                 logging.info("Epoch %d: %s improved from %.5f to %.5f, saving model to %s",
                              epoch + 1, self.monitor, self.best, cur, path)
             self.best = cur
+        if getattr(self.model, "rank", 0) != 0:
+            return  # data parallel: every rank keeps `best` in step, rank 0 alone writes
         if self.save_weights_only:
             self.model.save_weights(path)
         else:
