@@ -701,6 +701,56 @@ int pld_al_oracle(const float* gt, int n, int h, int w, const int32_t* pos_xy, i
                   int row_stride, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Test-set evaluation (evalset.hip): the ordinal pair tables and rankings of
+ * pldepth/data/providers/generic_ranking_provider.py, the ordinal pair error over such a table,
+ * and the resize of the Ibims / DIODE / TUM loaders. Each entry point is one launch for all n
+ * images. The random coordinates are drawn on the host in the reference's order and passed in.
+ * Pixel indices are carried as float32 like the reference's tables, so an image holds at most
+ * 2^24 pixels (PLD_ERR_ARG above).
+ * ------------------------------------------------------------------------------------------ */
+#define PLD_RANKING_MAX_L 64
+/* generic_ranking_provider.py:91-109 generate_ordinal_pairs after its draws: gt [n][h][w],
+ * coords [n][P][4] = (x0, y0, x1, y1) with x the row and y the column as there,
+ * out [n][P][5] = (x0 * w + y0, x1 * w + y1, relation, z0, z1), z = gt[x][y] and relation =
+ * get_depth_relation(z0, z1, tau) (depth_utils.py:5-21 in float32: +1 when (z0 + 1e-10) /
+ * (z1 + 1e-10) >= float32(1 + tau), -1 when <= float32(1 / (1 + tau)), else 0; tau < 0 stands
+ * for threshold=None, the plain comparison), multiplied by -1 when invert != 0. Coordinates
+ * inside the map are a PRECONDITION the caller checks; a point outside reads no memory and has
+ * depth 0. */
+int pld_ordinal_pairs(const float* gt, int n, int h, int w, const int32_t* coords, int P,
+                      double tau, int invert, float* out, void* stream);
+/* generic_ranking_provider.py:190-212 generate_rankings after its draws: gt [n][hw],
+ * idx [n][R][L] flat pixel indices, out [n][R][L][2] = (index, depth) per list, ordered by
+ * depth. invert == 0: descending, the reverse of a stable ascending sort by list position
+ * (np.argsort(.)[::-1]; equal depths: later position first, the rule of pld_al_oracle).
+ * invert != 0: that stable ascending order, and the depth column holds 1 / (z + 1) evaluated in
+ * double and rounded once (the reference's float64 buffer). NaN depths sort last in ascending
+ * order. L <= PLD_RANKING_MAX_L (PLD_ERR_UNSUPPORTED above). Indices in [0, hw) are a
+ * PRECONDITION the caller checks; an index outside reads no memory and has depth 0. */
+int pld_depth_rankings(const float* gt, int n, int64_t hw, const int32_t* idx, int R, int L,
+                       int invert, float* out, void* stream);
+/* The ordinal error over a table of pld_ordinal_pairs (the use the reference keeps z0 and z1
+ * for, generic_ranking_provider.py:108): pred [n][hw], pairs [n][P][5]. Per image,
+ * counted[i] = #pairs with relation != 0 and wrong[i] = #those whose sign(pred[p0] - pred[p1])
+ * differs from the relation (an equal or NaN prediction, or an index outside [0, hw), is
+ * wrong). use_tau != 0: the relation is not read from the table but recomputed from its z0, z1
+ * at tau and invert as pld_ordinal_pairs does. */
+int pld_ordinal_pair_error(const float* pred, int n, int64_t hw, const float* pairs, int P,
+                           double tau, int use_tau, int invert, int32_t* wrong, int32_t* counted,
+                           void* stream);
+/* skimage.transform.resize(x, (oh, ow)) with order 1, mode 'reflect' and anti-aliasing when
+ * shrinking (ibims.py:20-21, diode.py:34, tum.py:33-35), restated from scikit-image >= 0.19 as
+ * scipy.ndimage.gaussian_filter(mode='mirror') then scipy.ndimage.zoom(order=1, mode='mirror',
+ * grid_mode=True): x [n][h][w][c] -> y [n][oh][ow][c]. wy [ry + 1] and wx [rx + 1] are DEVICE
+ * arrays of doubles: the centre and one side of the normalised Gaussian of each axis (radius 0,
+ * weight 1: no blur), correlated with the border mirrored without repeating the edge pixel; then
+ * linear interpolation at src = (dst + 0.5) * in / out - 0.5, mirrored likewise. Accumulated in
+ * double, rounded once. */
+int pld_resize_antialias(const float* x, int n, int h, int w, int c, int oh, int ow,
+                         const double* wy, int ry, const double* wx, int rx, float* y,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * hipGraph capture of a whole stream-ordered step (replaces Keras' per-op dispatch)
  * ------------------------------------------------------------------------------------------ */
 int pld_graph_begin(void* stream);

@@ -9,6 +9,9 @@ Same names, arguments and results as the reference:
   * ``dcg_metric(model, test_im, test_gt, list_size=200)``    metrics.py:112-120
   * ``depth_edge_metric(op, gt, imsize=(224, 224))``          metrics.py:123-144
   * ``calc_depth_metrics(model, test_im, test_gt)``           metrics.py:147-156
+and, beyond the reference's module, ``ordinal_pair_error(model_or_pred, images, pairs, ...)``: the
+ordinal error over the pair tables of GenericHourglassPairRelationDataProvider
+(``pld_ordinal_pair_error``; pldepth_amd/test_data_eval.py reports it).
 The random pixel pairs / lists are drawn on the host with the reference's exact numpy calls
 (``np.random.seed(10)`` / ``np.random.seed(69)`` + ``np.random.choice(..., replace=False)``, which
 also leave the global numpy RNG in the same state); the comparisons, min-max normalisation,
@@ -144,6 +147,38 @@ def calc_err(model, test_im, test_gt, img_size=(448, 448)):
                  else test_gt[i:i + k]).reshape(k, -1)
         errs.append(K.ordinal_error(p, g, i0, i1).cpu().numpy())
     return float(np.mean(np.concatenate(errs))) if errs else float("nan")
+
+
+def ordinal_pair_error(model_or_pred, images, pairs, threshold=None, invert=False):
+    """The ordinal error over the pair tables of GenericHourglassPairRelationDataProvider
+    (``pairs`` [N, P, 5]: point0, point1, relation, z0, z1), in ``pld_ordinal_pair_error``.
+
+    ``model_or_pred``: a model, which then predicts ``images`` batch by batch, or the predictions
+    [N, H, W(, 1)] themselves (``images`` is not read). ``threshold=None`` takes the table's
+    relations; a number recomputes them from the table's depths at that threshold and ``invert``
+    (the provider's ``invert_relation_sign``). Returns ``(error, per_image_error, counted)``:
+    error = sum(wrong) / sum(counted) over the pairs whose relation is not 'equal', the same per
+    image (nan where an image has no such pair) and the per-image counts."""
+    pairs = _dev(pairs)
+    if hasattr(model_or_pred, "engine"):
+        wrong, counted = [], []
+        for i, k, pred in _predict_batches(model_or_pred, images):
+            w, c = K.ordinal_pair_error(pred.reshape(k, -1).contiguous(),
+                                        pairs[i:i + k].contiguous(), threshold, invert)
+            wrong.append(w)
+            counted.append(c)
+        if not wrong:
+            return float("nan"), np.zeros(0), np.zeros(0, np.int64)
+        wrong, counted = torch.cat(wrong), torch.cat(counted)
+    else:
+        pred = _dev(model_or_pred)
+        wrong, counted = K.ordinal_pair_error(pred.reshape(pred.shape[0], -1), pairs, threshold,
+                                              invert)
+    wrong, counted = wrong.cpu().numpy().astype(np.int64), counted.cpu().numpy().astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_image = wrong / counted
+        error = float(wrong.sum() / counted.sum()) if counted.sum() else float("nan")
+    return error, per_image, counted
 
 
 def calcDCG(rel_list):

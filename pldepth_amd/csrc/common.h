@@ -48,6 +48,18 @@ __device__ __forceinline__ float add_rn(float a, float b) {
   return a + b;
 }
 
+// ---- get_depth_relation (pldepth/data/depth_utils.py:5-21) on float32 depths, as NumPy 2
+// (NEP 50) evaluates it: the ratio in float32, compared with hi = float32(1 + tau) and
+// lo = float32(1 / (1 + tau)), which the caller forms in double. One definition for the sampler
+// (sampler.hip, tau = 0.03) and the evaluation pairs (evalset.hip). NaN gives 0.
+__device__ __forceinline__ int depth_relation32(float d1, float d2, float hi, float lo) {
+  const float eps = 1e-10f;
+  const float r = __fdiv_rn(add_rn(d1, eps), add_rn(d2, eps));
+  if (r >= hi) return 1;
+  if (r <= lo) return -1;
+  return 0;
+}
+
 // ---- activations (Keras semantics) ----
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SWISH = 2, ACT_SIGMOID = 3 };
 

@@ -160,12 +160,8 @@ __global__ void draw_kernel(const int* __restrict__ nvalid, int B, int per_img, 
 
 // ------------------------------------------------------------------ per-list sort + score
 __device__ __forceinline__ int depth_relation32(float d1, float d2) {
-  // pldepth/data/depth_utils.py:5-21 with tau = 0.03, float32 (NumPy 2 / NEP 50)
-  const float eps = 1e-10f;
-  const float r = __fdiv_rn(add_rn(d1, eps), add_rn(d2, eps));
-  if (r >= 1.03f) return 1;
-  if (r <= (float)(1.0 / 1.03)) return -1;  // float32(1/1.03), as NumPy casts the Python float
-  return 0;
+  // tau = 0.03; float32(1/1.03), as NumPy casts the Python float
+  return depth_relation32(d1, d2, 1.03f, (float)(1.0 / 1.03));
 }
 
 // NumPy float32 add.reduce of a contiguous array: 0 + pairwise_sum (oracle.sampler.pairwise_sum32)

@@ -11,6 +11,26 @@ import numpy as np
 from PIL import Image
 
 
+TESTING_ONLY_STR = "{} is intended to be used for testing only and, thus, this DAO does not " \
+                   "provide a {} set."
+
+
+class TFDatasetDataProvider(abc.ABC):
+    """data_meta.py:7-22: the base of the providers that turn a DAO's dataset into what the
+    model is fed (here: device tensors instead of TF datasets)."""
+
+    def __init__(self, model_params):
+        self.model_params = model_params
+
+    @abc.abstractmethod
+    def provide_train_dataset(self, base_ds, base_ds_gts=None):
+        pass
+
+    @abc.abstractmethod
+    def provide_val_dataset(self, base_ds, base_ds_gts=None):
+        pass
+
+
 class TFDataAccessObject(abc.ABC):
     @abc.abstractmethod
     def get_training_dataset(self):

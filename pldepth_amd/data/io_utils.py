@@ -1,8 +1,8 @@
 """Dataset-name dispatch (mirrors pldepth/data/io_utils.py:4-25): the names the drivers accept.
 
-Only HR-WSI has a data-access object in this build (pldepth_amd.data.dao.hr_wsi); the other
-datasets are evaluation-only in the reference (out of scope) and resolve to their
-enum value so that driver code parsing them runs unchanged.
+Every name has a data-access object (pldepth_amd.data.dao.dao_meta.get_dao_for_dataset_type):
+HR-WSI for training, validation and test, the others (Ibims, Sintel, DIODE, TUM) for test-set
+evaluation only, as in the reference.
 """
 from ..models.models_meta import StringEnum
 

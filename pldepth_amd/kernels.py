@@ -1213,6 +1213,105 @@ def al_oracle(gt, pos_xy, L, row_stride):
     return out
 
 
+# ---- test-set evaluation (evalset.hip) ----
+RANKING_MAX_L = CONST["PLD_RANKING_MAX_L"]
+MAX_INDEXED_PIXELS = 1 << 24  # flat pixel indices are carried as float32
+
+
+def _check_pixels(who, hw):
+    if hw > MAX_INDEXED_PIXELS:
+        raise ValueError(f"{who}: {hw} pixels per image; flat indices are stored as float32, "
+                         f"exact up to {MAX_INDEXED_PIXELS}")
+
+
+def ordinal_pairs(gt, coords, tau=0.03, invert=False):
+    """gt: [n, h, w] float32 device tensor; coords: host integers [n, P, 4] = (x0, y0, x1, y1),
+    x the row -> [n, P, 5] float32 device table (p0, p1, relation, z0, z1), see
+    pld_ordinal_pairs. tau=None: the plain comparison."""
+    n, h, w = gt.shape
+    _check_pixels("ordinal_pairs", h * w)
+    coords = np.asarray(coords)  # drawn on the host, and checked there before any launch
+    if coords.dtype.kind not in "iu" or coords.size == 0 or coords.ndim != 3 \
+            or coords.shape[0] != n or coords.shape[2] != 4:
+        raise ValueError(f"ordinal_pairs: expected non-empty integers [{n}, P, 4], got "
+                         f"{coords.dtype} {coords.shape}")
+    lim = np.array([h, w, h, w])
+    if coords.min() < 0 or (coords >= lim).any():
+        bad = coords[((coords < 0) | (coords >= lim)).any(-1)][0]
+        raise ValueError(f"ordinal_pairs: point {tuple(int(v) for v in bad)} outside a map of "
+                         f"{h} x {w} pixels")
+    P = coords.shape[1]
+    c = torch.from_numpy(np.ascontiguousarray(coords, np.int32)).to(gt.device)
+    out = torch.empty((n, P, 5), dtype=torch.float32, device=gt.device)
+    lib().pld_ordinal_pairs(ptr(_f32(gt)), n, h, w, ptr(c), P,
+                            -1.0 if tau is None else float(tau), int(bool(invert)), ptr(out),
+                            stream())
+    return out
+
+
+def depth_rankings(gt, idx, invert=False):
+    """gt: [n, h, w] or [n, hw] float32 device tensor; idx: host integers [n, R, L] flat pixel
+    indices -> [n, R, L, 2] float32 device rankings (index, depth), see pld_depth_rankings."""
+    n, hw = gt.shape[0], gt[0].numel()
+    _check_pixels("depth_rankings", hw)
+    idx = np.asarray(idx)
+    if idx.dtype.kind not in "iu" or idx.ndim != 3 or idx.size == 0 or idx.shape[0] != n:
+        raise ValueError(f"depth_rankings: expected non-empty integers [{n}, R, L], got "
+                         f"{idx.dtype} {idx.shape}")
+    if idx.min() < 0 or idx.max() >= hw:
+        bad = int(idx.min() if idx.min() < 0 else idx.max())
+        raise ValueError(f"depth_rankings: index {bad} outside an image of {hw} pixels")
+    _, R, L = idx.shape
+    d = torch.from_numpy(np.ascontiguousarray(idx, np.int32)).to(gt.device)
+    out = torch.empty((n, R, L, 2), dtype=torch.float32, device=gt.device)
+    lib().pld_depth_rankings(ptr(_f32(gt)), n, hw, ptr(d), R, L, int(bool(invert)), ptr(out),
+                             stream())
+    return out
+
+
+def ordinal_pair_error(pred, pairs, tau=None, invert=False):
+    """pred: [n, ...] float32 device predictions of hw pixels each; pairs: [n, P, 5] float32
+    device table of ordinal_pairs -> (wrong [n], counted [n]) int32 device tensors, see
+    pld_ordinal_pair_error. tau=None: the table's relations; else they are recomputed from its
+    depths at tau and invert."""
+    n, hw = pred.shape[0], pred[0].numel()
+    _check_pixels("ordinal_pair_error", hw)
+    assert pairs.dim() == 3 and pairs.shape[0] == n and pairs.shape[2] == 5, tuple(pairs.shape)
+    wrong = torch.empty(n, dtype=torch.int32, device=pred.device)
+    counted = torch.empty(n, dtype=torch.int32, device=pred.device)
+    lib().pld_ordinal_pair_error(ptr(_f32(pred)), n, hw, ptr(_f32(pairs)), pairs.shape[1],
+                                 0.0 if tau is None else float(tau), int(tau is not None),
+                                 int(bool(invert)), ptr(wrong), ptr(counted), stream())
+    return wrong, counted
+
+
+def antialias_taps(n_in, n_out):
+    """The centre and one side of the normalised Gaussian skimage.transform.resize blurs an axis
+    with before it shrinks it from n_in to n_out (float64): sigma = max(0, (n_in / n_out - 1) /
+    2), radius int(4 sigma + 0.5), weights exp(-0.5 / sigma^2 * d^2) / sum as
+    scipy.ndimage.gaussian_filter forms them. [1.] when nothing is blurred."""
+    sigma = max(0.0, (n_in / n_out - 1) / 2)
+    radius = int(4.0 * sigma + 0.5)
+    if sigma <= 0 or radius == 0:
+        return np.ones(1)
+    d = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * d ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[radius:])
+
+
+def resize_antialias(x, oh, ow, out=None):
+    """x: [n, h, w, c] float32 device tensor -> [n, oh, ow, c]: skimage.transform.resize(order 1,
+    mode 'reflect', anti-aliasing when shrinking), see pld_resize_antialias."""
+    n, h, w, c = x.shape
+    out = torch.empty((n, oh, ow, c), dtype=torch.float32, device=x.device) if out is None else out
+    wy, wx = antialias_taps(h, oh), antialias_taps(w, ow)
+    taps = torch.from_numpy(np.concatenate([wy, wx])).to(x.device)  # one upload
+    lib().pld_resize_antialias(ptr(_f32(x.contiguous())), n, h, w, c, oh, ow, ptr(taps[:len(wy)]),
+                               len(wy) - 1, ptr(taps[len(wy):]), len(wx) - 1, ptr(out), stream())
+    return out
+
+
 # ---- HR-WSI resizing (pld_resize_bilinear / pld_resize_nearest) ----
 def resize(x, oh, ow, method="bilinear", out=None):
     """x: [n, h, w, c] float32 device tensor -> [n, oh, ow, c] (tf.image.resize, TF2 semantics)."""

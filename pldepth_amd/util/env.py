@@ -18,7 +18,10 @@ CONFIG_FILE = "conf/run.ini"
 CONFIG_FILE_ENCODING = "utf-8-sig"
 _DEFAULTS = {
     "LOGGING": {"LOG_LEVEL": "INFO", "TENSORBOARD_LOG_DIR": os.path.join(ROOT_DIR, "logs")},
-    "DATA": {"CACHE_PATH_PREFIX": os.path.join(ROOT_DIR, "cache")},
+    "DATA": {"CACHE_PATH_PREFIX": os.path.join(ROOT_DIR, "cache"),
+             # dataset roots read by data/dao/dao_meta.py (dao_meta.py:9-22)
+             **{name + "_ROOT_PATH": os.path.join(ROOT_DIR, "data", name.lower())
+                for name in ("HR_WSI", "IBIMS", "DIODE", "SINTEL", "TUM")}},
 }
 
 
