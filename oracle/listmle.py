@@ -55,23 +55,40 @@ def listmle_fwd_bwd(s, labels):
     return nll, g
 
 
-def hourglass_nll(y_true, y_pred, batch_size, ranking_size):
+def hourglass_nll(y_true, y_pred, batch_size, ranking_size, out_of_range_zero=False,
+                  return_nll=False):
     """``HourglassNegativeLogLikelihood(ranking_size, batch_size)(y_true, y_pred)``.
 
     y_true: [B, R, L, 2] (float32 flat index, gt); y_pred: [B, H, W(, 1)].
-    Returns (loss fp64 scalar, dloss/dy_pred fp64 with y_pred's shape).
+    Returns (loss fp64 scalar, dloss/dy_pred fp64 with y_pred's shape), and the per-list nll
+    [B*R] fp64 as a third value with ``return_nll``.
+
+    ``out_of_range_zero`` restates the HIP kernel's documented rule for an index that lies outside
+    [0, H*W) after truncation (TF's GPU gather yields 0 there): the element gathers 0.0 and
+    receives no gradient, and still takes part in its list with that logit. Off (the default),
+    such an index is an error (numpy raises), as before.
     """
     B, L = batch_size, ranking_size
     rk = np.asarray(y_true, np.float32).reshape(B, -1, L, 2)
     pred = np.asarray(y_pred, np.float64).reshape(B, -1)
-    idx = rk[..., 0].reshape(B, -1).astype(np.int32)  # tf.cast(float32 -> int32) truncates
-    s = np.take_along_axis(pred, idx, axis=1).reshape(-1, L)
+    HW = pred.shape[1]
+    if out_of_range_zero:
+        # truncate in floating point: 2.0**31 and beyond have no int32 value to compare
+        tr = np.trunc(rk[..., 0].reshape(B, -1).astype(np.float64))
+        inr = (tr >= 0) & (tr < HW)
+        idx = np.where(inr, tr, 0.0).astype(np.int64)
+        s = np.where(inr, np.take_along_axis(pred, idx, axis=1), 0.0).reshape(-1, L)
+    else:
+        idx = rk[..., 0].reshape(B, -1).astype(np.int32)  # tf.cast(float32 -> int32) truncates
+        inr = np.ones(idx.shape, bool)
+        s = np.take_along_axis(pred, idx, axis=1).reshape(-1, L)
     lab = rk[..., 1].reshape(-1, L)
     nll, g = listmle_fwd_bwd(s, lab)
     N = nll.shape[0]
     loss = nll.mean()
     dpred = np.zeros_like(pred)
-    gb = (g / N).reshape(B, -1)
+    gb = np.where(inr, (g / N).reshape(B, -1), 0.0)
     for b in range(B):
         np.add.at(dpred[b], idx[b], gb[b])
-    return loss, dpred.reshape(np.shape(y_pred))
+    dpred = dpred.reshape(np.shape(y_pred))
+    return (loss, dpred, nll) if return_nll else (loss, dpred)

@@ -152,6 +152,97 @@ def test_hourglass_loss_gather_and_scatter():
         assert abs((lp - lm) / (2 * eps) - dpred.reshape(B, -1)[b, p]) < 1e-7
 
 
+def test_hourglass_out_of_range_keyword_is_inert_on_in_range_input():
+    rng = np.random.default_rng(4)
+    B, H, W, R, L = 2, 5, 6, 3, 4
+    pred = rng.standard_normal((B, H, W, 1))
+    idx = rng.integers(0, H * W, (B, R, L)) + rng.random((B, R, L)) * 0.9  # fractional: truncated
+    lab = rng.permutation(B * R * L).reshape(B, R, L) / (B * R * L)
+    lab[1, 2, 0] = -1.0
+    y = np.stack([idx.astype(np.float32), lab.astype(np.float32)], -1)
+    loss, dpred = LM.hourglass_nll(y, pred, B, L)
+    loss_k, dpred_k, nll_k = LM.hourglass_nll(y, pred, B, L, out_of_range_zero=True,
+                                              return_nll=True)
+    assert loss_k == loss and np.array_equal(dpred_k, dpred)
+    assert nll_k.shape == (B * R,) and nll_k.mean() == loss
+
+
+def test_hourglass_out_of_range_hand_worked_list():
+    """One list (a, OUT, c) in label order over a 4-pixel image: the out-of-range element is a
+    0.0 logit in the middle of the list. nll = log(e^a + 1 + e^c) - a + log(1 + e^c) - 0 + 0."""
+    a, c = 0.7, -1.3
+    pred = np.array([[5.0, a, c, -4.0]])
+    S1, S2 = np.exp(a) + 1.0 + np.exp(c), 1.0 + np.exp(c)
+    want_nll = np.log(S1) - a + np.log(S2)
+    want = np.array([[0.0, np.exp(a) / S1 - 1.0, np.exp(c) / S1 + np.exp(c) / S2, 0.0]])
+    for out in (7.0, 4.0, -1.0, 2.0 ** 31):
+        y = np.array([[1.0, 0.9], [out, 0.5], [2.0, 0.1]], np.float32).reshape(1, 1, 3, 2)
+        loss, dpred, nll = LM.hourglass_nll(y, pred, 1, 3, out_of_range_zero=True,
+                                            return_nll=True)
+        np.testing.assert_allclose(loss, want_nll, rtol=1e-14)
+        np.testing.assert_allclose(nll, [want_nll], rtol=1e-14)
+        np.testing.assert_allclose(dpred, want, rtol=1e-13, atol=0)
+        assert dpred[0, 0] == 0.0 and dpred[0, 3] == 0.0
+    y = np.array([[1.0, 0.9], [7.0, 0.5], [2.0, 0.1]], np.float32).reshape(1, 1, 3, 2)
+    with pytest.raises(IndexError):  # the default still refuses such an index
+        LM.hourglass_nll(y, pred, 1, 3)
+
+
+# -------------------------------------------------------------------------------- Adam oracle
+def _adam_case(grad_scale):
+    """tests/test_kernels_gpu.py::test_adam_amsgrad_matches_oracle's five steps."""
+    from oracle.adam import adam_amsgrad_step, adam_amsgrad_step64
+    rng = np.random.default_rng(0)
+    n = 1027
+    p = rng.standard_normal(n).astype(np.float32)
+    st = [np.zeros(n, np.float32) for _ in range(3)]
+    for step in range(1, 6):
+        g = rng.standard_normal(n).astype(np.float32) * (0.1 if step % 2 else 3.0)
+        new32 = adam_amsgrad_step(p, g, *st, lr=0.01, step=step, grad_scale=grad_scale)
+        new64 = adam_amsgrad_step64(p, g, *st, lr=0.01, step=step, grad_scale=grad_scale)
+        yield p, g, new32, new64
+        p, st = new32[0], list(new32[1:])
+
+
+@pytest.mark.parametrize("grad_scale", [1.0, 0.5, 0.3])
+def test_adam_float64_step_agrees_with_float32_step(grad_scale):
+    """Each step from the same float32 state: the two differ by float32 rounding. m, v and vhat
+    take a few roundings each; the update dp inherits the relative error of alpha, where
+    1 - b2^t amplifies the half-ulp of the float32 power by b2^t / (2 (1 - b2^t)) <= 500."""
+    eps32 = 2.0 ** -24
+    for p, g, new32, new64 in _adam_case(grad_scale):
+        assert all(a.dtype == np.float32 for a in new32)
+        assert all(a.dtype == np.float64 for a in new64)
+        for a32, a64 in zip(new32[1:], new64[1:]):
+            assert np.abs(a32 - a64).max() <= 8 * eps32 * np.abs(a64).max()
+        dp32, dp64 = new32[0].astype(np.float64) - p, new64[0] - p
+        # half an ulp of p itself (|p| < 8) plus the amplified rounding of alpha
+        assert np.abs(dp32 - dp64).max() <= 8 * eps32 + 600 * eps32 * np.abs(dp64).max()
+
+
+def test_adam_grad_scale_is_one_float32_product():
+    from oracle.adam import adam_amsgrad_step, adam_amsgrad_step64
+    rng = np.random.default_rng(1)
+    n = 64
+    p, g = (rng.standard_normal(n).astype(np.float32) for _ in range(2))
+    m = rng.standard_normal(n).astype(np.float32) * np.float32(0.1)
+    v = rng.random(n).astype(np.float32)
+    vh = rng.random(n).astype(np.float32)
+    for step_fn in (adam_amsgrad_step, adam_amsgrad_step64):
+        # a power of two scales exactly: same result as the pre-scaled gradient
+        a = step_fn(p, g, m, v, vh, lr=0.01, step=3, grad_scale=0.25)
+        b = step_fn(p, g * np.float32(0.25), m, v, vh, lr=0.01, step=3)
+        assert all(np.array_equal(x, y) for x, y in zip(a, b))
+        # and the default leaves the gradient alone
+        c = step_fn(p, g, m, v, vh, lr=0.01, step=3, grad_scale=1.0)
+        d = step_fn(p, g, m, v, vh, lr=0.01, step=3)
+        assert all(np.array_equal(x, y) for x, y in zip(c, d))
+    # the float32 step rounds the product to float32, as the kernel does
+    a = adam_amsgrad_step(p, g, m, v, vh, lr=0.01, step=3, grad_scale=0.3)
+    b = adam_amsgrad_step(p, g * np.float32(0.3), m, v, vh, lr=0.01, step=3)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
 def test_redweb_oracle_counts_match_survey():
     """142.54 GFLOP per 448x448 image per train step, 53,120
     encoder-BN parameters, ~8.65 M trainable in total."""
