@@ -34,7 +34,8 @@ enum {
   PLD_SAMPLER_PURE = 0,   /* PurelyMaskedRandomSamplingStrategy     sampling.py:106-150, f=0.8 */
   PLD_SAMPLER_MASKED = 1, /* MaskedRandomSamplingStrategy           sampling.py:153-170, f=1.5 */
   PLD_SAMPLER_THRESH = 2, /* ThresholdedMaskedRandomSamplingStrategy sampling.py:172-208, f=1.5 */
-  PLD_SAMPLER_INFO = 3    /* InformationScoreBasedSampling          sampling.py:211-242, f=5   */
+  PLD_SAMPLER_INFO = 3,   /* InformationScoreBasedSampling          sampling.py:211-242, f=5   */
+  PLD_SAMPLER_RANDOM = 4  /* RandomSamplingStrategy (unmasked)      sampling.py:48-103,  f=1.5 */
 };
 
 const char* pld_last_error(void);
@@ -537,7 +538,22 @@ int pld_dwconv_dgrad_se_bn(const float* dy, const float* x, int n, int h, int w,
  *       (seed, step, image_offset + b, cand*L + slot) — independent of the GPU count.
  *   pld_sampler_rank: gather + per-list descending sort + strategy score + top-R selection,
  *       bit-identical to oracle/sampler.py for the same draws. out [B][R_out][L][2] float32
- *       (R_out = R, or floor(0.8R) for PURE).
+ *       (R_out = R, or floor(0.8R) for PURE). The strategies' default arguments: tau = 0.03,
+ *       penalty = -1000, the enum's factors, a mask at the image's resolution.
+ *   pld_sampler_rank_ex: the same with every argument of the reference's classes at run time:
+ *       n_cand = int(R * batch_size_factor) (formed by the caller, sampling.py:55), tau
+ *       (`threshold`, depth_utils.py:16-18: hi = float32(1 + tau), lo = float32(1 / (1 + tau)),
+ *       formed in double) and penalty (`equality_penalty`: float32 for THRESH, sampling.py:202;
+ *       float64 for INFO, sampling.py:237). The consistency mask may have another resolution
+ *       than gt: valid_idx / nvalid / draws then live on the mask grid [mask_h][mask_w] (stride
+ *       mask_h*mask_w per image) and a drawn (mr, mc) maps to the pixel
+ *       (int(mr * (H / mask_h)), int(mc * (W / mask_w))), sampling.py:115-116,125-129;
+ *       gt_minmax stays that of the whole gt (pld_sampler_minmax, sampling.py:219-220).
+ *       PLD_SAMPLER_RANDOM (sampling.py:89-103): no mask, valid_idx and nvalid NULL, a draw is
+ *       the flat pixel r*W + c; lists keep their draw order and are scored by the float64 sum
+ *       of adjacent gaps of their depths sorted descending (sampling.py:34-42).
+ *       R_out = R, or min(n_cand, R) for PURE (sampling.py:150). Limits: L <= 512,
+ *       H*W < 2^24, n_cand <= 19200 (LDS selection buffer).
  * ------------------------------------------------------------------------------------------ */
 size_t pld_sampler_workspace_size(int B, int H, int W, int R, int L, int strategy);
 int pld_sampler_compact(const float* mask, int B, int H, int W, const float* gt, int* valid_idx,
@@ -553,6 +569,16 @@ int pld_sampler_rank(const float* gt, const int* valid_idx, const int* nvalid,
                      const float* gt_minmax, const int* draws, int B, int H, int W, int R, int L,
                      int strategy, float* out, void* ws, void* stream);
 int pld_sampler_candidates(int R, int strategy); /* int(R * factor) */
+/* bytes[0] = workspace of pld_sampler_rank_ex (candidate lists and their scores) */
+int pld_sampler_rank_ex_workspace_size(int B, int n_cand, int L, size_t* bytes);
+int pld_sampler_rank_ex(const float* gt, const int* valid_idx, const int* nvalid,
+                        const float* gt_minmax, const int* draws, int B, int H, int W,
+                        int mask_h, int mask_w, int R, int L, int n_cand, int strategy,
+                        double tau, double penalty, float* out, void* ws, size_t ws_bytes,
+                        void* stream);
+/* gt_minmax [B][2] = np.amin(gt), np.amax(gt) per image (sampling.py:219-220), for a mask whose
+ * grid is not the image's (pld_sampler_compact gives them when it is) */
+int pld_sampler_minmax(const float* gt, int B, int H, int W, float* gt_minmax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * HR-WSI data access: tf.image.resize of decoded images / depth maps (bilinear)

@@ -11,7 +11,12 @@ sampler launch (Philox draws keyed by seed / batch counter / image position) ins
 per-image Python call under the GIL. Batches are (x [B,H,W,3], y [B,R,L,2]) device tensors.
 
 With ``device_resident=True`` the arrays are uploaded once and the gather and flip of a batch are
-one kernel as well (pld_batch_gather_flip); the host keeps only the index work.
+one kernel as well (pld_batch_gather_flip); the host keeps only the index work. Consistency masks
+of another resolution than the images (the sampler scales their positions, sampling.py:125-129)
+take a second launch of that kernel.
+
+``sampling_eq_threshold`` is the training sampler's tau; the validation sampler keeps the default
+0.03, as in the reference (:21-22).
 
 Data parallel (``rank``, ``world``): ``batch_size`` stays the per-replica batch B and the global
 batch is G = world * B. Every rank holds the whole dataset and runs the same host RNG stream; rank
@@ -140,9 +145,15 @@ class _ResidentTrainIterable(object):
         rng = np.random.default_rng(p.seed)
         n = len(self.imgs)
         step = 0
+        own_grid = self.masks.shape[1:] != self.gts.shape[1:]  # masks of another resolution
         while True:  # repeat()
             for idx, flip in _epoch_batches(rng, n, B, p.world, p.rank, p.augmentation):
-                x, g, m = K.batch_gather_flip(self.imgs, self.gts, self.masks, idx, flip)
+                if own_grid:  # gathered and flipped by a call of their own, as 1-channel images
+                    x, g, _ = K.batch_gather_flip(self.imgs, self.gts, None, idx, flip)
+                    m = K.batch_gather_flip(self.masks.unsqueeze(-1), None, None, idx,
+                                            flip)[0].squeeze(-1)
+                else:
+                    x, g, m = K.batch_gather_flip(self.imgs, self.gts, self.masks, idx, flip)
                 y = strategy.sample_batch_gpu(g, m, R, seed=p.seed, step=step,
                                               image_offset=p.rank * B)
                 step += 1

@@ -1056,6 +1056,38 @@ def sampler_rank(gt, valid_idx, nvalid, gt_minmax, draws, R, L, strategy, out):
     return out
 
 
+# pld_sampler_rank_ex also takes the unmasked RandomSamplingStrategy
+SAMPLER_EX = dict(SAMPLER, random=CONST["PLD_SAMPLER_RANDOM"])
+
+
+def sampler_rank_ex_workspace_size(B, n_cand, L):
+    need = C.c_size_t()
+    lib().pld_sampler_rank_ex_workspace_size(B, n_cand, L, C.byref(need))
+    return need.value
+
+
+def sampler_rank_ex(gt, valid_idx, nvalid, gt_minmax, draws, R, L, strategy, out, n_cand,
+                    tau=0.03, penalty=-1000, mask_shape=None):
+    """sampler_rank with the strategy classes' arguments: n_cand = int(R * batch_size_factor),
+    tau, penalty and the mask's grid (mask_shape (h, w); None: the image's). valid_idx / nvalid
+    index the mask grid; both are None for the unmasked "random" strategy."""
+    B, H, W = gt.shape
+    mh, mw = (H, W) if mask_shape is None else mask_shape
+    need = sampler_rank_ex_workspace_size(B, n_cand, L)
+    ws = workspace(need, "sampler_ex")
+    lib().pld_sampler_rank_ex(ptr(gt), ptr(valid_idx), ptr(nvalid), ptr(gt_minmax), ptr(draws),
+                              B, H, W, mh, mw, R, L, n_cand, SAMPLER_EX[strategy], float(tau),
+                              float(penalty), ptr(out), ptr(ws), need, stream())
+    return out
+
+
+def sampler_minmax(gt, gt_minmax):
+    """gt [B,H,W] -> gt_minmax [B,2]: np.amin / np.amax per image (the Info strategy's bounds when
+    the mask is on another grid and sampler_compact cannot give them)."""
+    B, H, W = gt.shape
+    lib().pld_sampler_minmax(ptr(gt), B, H, W, ptr(gt_minmax), stream())
+
+
 # ---- test-pass metrics (pld_ordinal_error / pld_dcg_ratio) ----
 def ordinal_error(pred, gt, idx0, idx1):
     """pred, gt: [n, hw] float32 device tensors; idx0/idx1: int32 device indices -> [n] float64."""
