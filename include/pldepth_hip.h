@@ -57,6 +57,32 @@ int pld_listmle_fwd_bwd(const float* pred, const float* y_true, int B, int HW, i
                         float* nll, float* loss, float* dpred, int zero_dpred, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Position-weighted ListMLE (p-ListMLE), sample weights and reductions: what the reference's
+ * losses forward into tensorflow_ranking and Keras when their declared arguments are used
+ * (pldepth/losses/nll_loss.py:11-16, 33-40: ListMLELoss(lambda_weight=...), Keras
+ * Loss.__call__(sample_weight=...) and reduction=). Gather, validity, sort by label, tie order
+ * and the scatter-add are pld_listmle_fwd_bwd's. With t_r the sorted max-shifted logits,
+ * r = 1..L, and C_r = sum_{j>=r} exp(t_j - m):
+ *   rank_w [L]     w_r = rank_discount_fn(float32(r)): tfr ListMLELambdaWeight.individual_weights
+ *                  (ones_like(labels) * rank_discount_fn(range(L) + 1)); NULL = all ones
+ *                  nll_n = sum_r w_r (log C_r - (t_r - m));
+ *                  d nll_n / d t_k = exp(t_k - m) sum_{r<=k} w_r / C_r - w_k
+ *   list_w         s_n, Keras compute_weighted_loss: [B*R], one weight per list, or [B], one per
+ *                  image for all its R lists, when list_w_per_image != 0; NULL = all ones
+ *   reduction      PLD_REDUCE_MEAN: loss = sum_n s_n nll_n / (B*R) (Keras SUM_OVER_BATCH_SIZE: the
+ *                  list count, not the weight sum); PLD_REDUCE_SUM: loss = sum_n s_n nll_n
+ *   nll    [B*R]   s_n nll_n
+ *   dpred  [B][HW] d loss / d pred; zeroed first when zero_dpred != 0, else added to
+ * pred, y_true, L (1..512) and invalid elements (exactly 0 gradient) as pld_listmle_fwd_bwd.
+ * ------------------------------------------------------------------------------------------ */
+#define PLD_REDUCE_MEAN 0
+#define PLD_REDUCE_SUM 1
+int pld_listmle_weighted_fwd_bwd(const float* pred, const float* y_true, int B, int HW, int R,
+                                 int L, const float* rank_w, const float* list_w,
+                                 int list_w_per_image, int reduction, float* nll, float* loss,
+                                 float* dpred, int zero_dpred, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer: replaces keras.optimizers.Adam(lr, amsgrad=True) (pldepth/PLDepth.py:133), i.e. TF
  * ResourceApplyAdamWithAmsgrad on every trainable variable, fused over one flat buffer:
  *   alpha = lr*sqrt(1-b2^t)/(1-b1^t); g' = grad*grad_scale; m += (g'-m)(1-b1);

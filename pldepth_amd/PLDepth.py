@@ -11,6 +11,9 @@ Differences from the reference driver, all outside the accelerated path (SURVEY 
     GPU (``pld_batch_gather_flip``) instead of on the host;
   * no wandb / mlflow: metrics go to stdout and ``--log_jsonl``;
   * ``--input_size`` (the reference hard-codes 224 here and 448 in run_scripts/test_sampling.py);
+  * ``--listmle_discount {none,log,pow2}``: position weights of the loss (p-ListMLE: rank r
+    weighs 1/log2(1+r) or 2^(1-r)), passed as the loss's ``lambda_weight``; ``none`` (default)
+    is the reference's plain ListMLE;
   * ``--gpus N``: data-parallel training, one process per GPU (``--batch_size`` stays the per-GPU
     batch). Started without a launcher, the command runs its N ranks as one
     ``torch.distributed.run`` child and returns that child's exit code; rank 0 prints, logs,
@@ -26,6 +29,7 @@ import click
 import numpy as np
 
 from .losses.losses_meta import DepthLossType
+from .losses.lambda_weights import lambda_weight_by_name
 from .losses.nll_loss import HourglassNegativeLogLikelihood
 from .models.models_meta import ModelParameters, get_model_type_by_name
 from .models.PLDepthNet import get_pl_depth_net
@@ -78,6 +82,14 @@ def steps_per_epoch_for(ds_size, batch_size, world=1):
     return max(1, int((ds_size * 14 / 15) / (batch_size * world)))
 
 
+def build_loss(ranking_size, batch_size, listmle_discount='none'):
+    """The training loss of ``--listmle_discount``: plain ListMLE for ``none`` (the reference's
+    loss, PLDepth.py:128), else p-ListMLE with the named rank discount as its lambda weight."""
+    return HourglassNegativeLogLikelihood(
+        ranking_size=ranking_size, batch_size=batch_size,
+        lambda_weight=lambda_weight_by_name(listmle_discount, ranking_size))
+
+
 def _argv(params):
     """The command line that parses back to `params` (every option is `--name value`)."""
     return [a for k, v in params.items() if v is not None for a in (f"--{k}", str(v))]
@@ -109,6 +121,10 @@ def _argv(params):
 @click.option('--device_data', default=False, type=click.BOOL,
               help='keep the train and val sets in device memory and gather each batch there '
               '(same batches as the host path)')
+@click.option('--listmle_discount', default='none',
+              type=click.Choice(['none', 'log', 'pow2']),
+              help='position weights of the ListMLE loss (p-ListMLE): rank r weighs 1/log2(1+r) '
+              '(log) or 2^(1-r) (pow2); none = plain ListMLE')
 @click.option('--gpus', default=None, type=click.INT,
               help='data-parallel ranks, one process per GPU; --batch_size is per GPU '
               '(default: WORLD_SIZE under a launcher, else 1)')
@@ -145,7 +161,8 @@ def perform_pldepth_experiment(gpus=None, dist_backend=None, **params):
 def run_experiment(model_name, epochs, batch_size, seed, ranking_size, rankings_per_image,
                    initial_lr, equality_threshold, model_checkpoints, load_model_path,
                    augmentation, warmup, sampling_type, lr_multi, ds_size, input_size, data_npz,
-                   save_path, log_jsonl, hr_wsi_path='', device_data=False, rank=0, world=1):
+                   save_path, log_jsonl, hr_wsi_path='', device_data=False,
+                   listmle_discount='none', rank=0, world=1):
     """One rank's run (world 1: the whole run). With world > 1 the default process group is
     initialised: compile() makes the model a data-parallel replica of it."""
     np.random.seed(seed)
@@ -199,7 +216,7 @@ def run_experiment(model_name, epochs, batch_size, seed, ranking_size, rankings_
     schedule = SGDRScheduler(min_lr=initial_lr * (1 / lr_multi), max_lr=initial_lr,
                              steps_per_epoch=steps_per_epoch, lr_decay=0.9, cycle_length=epochs,
                              mult_factor=1)
-    loss_fn = HourglassNegativeLogLikelihood(ranking_size=ranking_size, batch_size=batch_size)
+    loss_fn = build_loss(ranking_size, batch_size, listmle_discount)
     model.compile(loss=loss_fn, optimizer=Adam(learning_rate=initial_lr, amsgrad=True))
     if load_model_path:
         model.load_weights(load_model_path)

@@ -82,6 +82,30 @@ def listmle_fwd_bwd(pred, y_true, B, R, L, dpred=None, nll=None, loss=None, zero
     return loss, dpred, nll
 
 
+REDUCE = {"mean": CONST["PLD_REDUCE_MEAN"], "sum": CONST["PLD_REDUCE_SUM"]}
+
+
+def listmle_weighted_fwd_bwd(pred, y_true, B, R, L, rank_w=None, list_w=None,
+                             list_w_per_image=False, reduction="mean", dpred=None, nll=None,
+                             loss=None, zero_dpred=True):
+    """pld_listmle_weighted_fwd_bwd: rank_w float32 [L] (None: ones), list_w float32 [B*R], or
+    [B] with list_w_per_image (None: ones), reduction "mean" | "sum". nll receives s_n nll_n."""
+    HW = pred.numel() // B
+    if rank_w is not None and _f32(rank_w).numel() != L:
+        raise ValueError(f"rank_w holds {rank_w.numel()} weights, not L = {L}")
+    if list_w is not None and _f32(list_w).numel() != (B if list_w_per_image else B * R):
+        raise ValueError(f"list_w holds {list_w.numel()} weights, not "
+                         f"{B if list_w_per_image else B * R}")
+    dpred = torch.empty_like(pred) if dpred is None else dpred
+    nll = torch.empty(B * R, dtype=torch.float32, device=pred.device) if nll is None else nll
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device) if loss is None else loss
+    lib().pld_listmle_weighted_fwd_bwd(ptr(_f32(pred)), ptr(_f32(y_true)), B, HW, R, L,
+                                       ptr(rank_w), ptr(list_w), int(bool(list_w_per_image)),
+                                       REDUCE[reduction], ptr(nll), ptr(loss), ptr(dpred),
+                                       int(zero_dpred), stream())
+    return loss, dpred, nll
+
+
 # ------------------------------------------------------------------------------- optimizer
 def adam_amsgrad(param, grad, m, v, vhat, lr, step, beta1=0.9, beta2=0.999, eps=1e-7,
                  grad_scale=1.0):

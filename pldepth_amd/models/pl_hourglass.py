@@ -67,10 +67,22 @@ class FullyFledgedModel(object):
         here: backend PLD_DP_BACKEND, default nccl = RCCL), and every rank must hold the same
         parameters and frozen weights (same seed or same weights file; checked, not broadcast).
         A group given at world 1 keeps the trainer's single-graph step (it has nothing to
-        exchange); the loss and statistics collectives then run over that one rank."""
+        exchange); the loss and statistics collectives then run over that one rank.
+        The training step takes the loss's lambda weights (``loss.rank_weights``) and reduction:
+        ``"none"`` is refused (a step needs a scalar), and so is ``"sum"`` at world > 1, where
+        the 1/world gradient scale would turn it into a mean over ranks. A loss without those
+        attributes, or with both at their defaults, trains through the unweighted call."""
         from .. import dp
         from ..optimizers import Adam
         from ..trainer import ReplicaTrainer
+        loss_kw = {}
+        reduction = getattr(loss, "reduction", "mean")
+        if reduction == "none":
+            raise ValueError("compile(): a loss with reduction 'none' cannot drive training")
+        if reduction != "mean":
+            loss_kw["reduction"] = reduction
+        if getattr(loss, "rank_weights", None) is not None:
+            loss_kw["rank_weights"] = loss.rank_weights
         self.loss = loss
         self.optimizer = optimizer if optimizer is not None else Adam(amsgrad=True)
         eng = self.engine
@@ -79,6 +91,9 @@ class FullyFledgedModel(object):
         rank, world, pg = distribute
         if not 0 <= rank < world:
             raise ValueError(f"rank {rank} outside a world of {world}")
+        if reduction == "sum" and world > 1:
+            raise ValueError("compile(): reduction 'sum' on a data-parallel replica: the 1/world "
+                             "gradient scale would turn it into a mean over ranks")
         self.rank, self.world = rank, world
         self.distributed = world > 1 or pg is not None
         dist_kw = {}
@@ -100,7 +115,7 @@ class FullyFledgedModel(object):
         self.trainer = ReplicaTrainer((eng.H, eng.W, 3), eng.B, loss.ranking_size, 1,
                                       engine=eng, gpu_sampler=False,
                                       beta_1=self.optimizer.beta_1, beta_2=self.optimizer.beta_2,
-                                      epsilon=self.optimizer.epsilon, **dist_kw)
+                                      epsilon=self.optimizer.epsilon, **dist_kw, **loss_kw)
         if self.distributed:
             self._check_replicas()
         self._captured = False
@@ -110,18 +125,25 @@ class FullyFledgedModel(object):
             keras_h5.load_optimizer_state(self, pending)
             self._pending_optimizer_state = None
 
-    def train_on_batch(self, x, y, return_loss=True):
-        """One optimizer step on (x [B,H,W,3], y [B,R,L,2]); returns the batch loss (float)."""
+    def train_on_batch(self, x, y, sample_weight=None, return_loss=True):
+        """One optimizer step on (x [B,H,W,3], y [B,R,L,2]); returns the batch loss (float).
+        ``sample_weight``: a scalar, one weight per list ([B*R] or [B*R,1]) or one per image
+        ([B] or [B,1]), as the loss's own ``sample_weight``. The first step that gives weights
+        after a capture made without them captures the step again, once; later steps without
+        weights run the same captured step on weights of one."""
         if self.trainer is None:
             raise RuntimeError("compile() the model first")
         tr = self.trainer
-        if self._captured and torch.as_tensor(y).numel() != tr.y_true.numel():
+        if self._captured and (torch.as_tensor(y).numel() != tr.y_true.numel()
+                               or (sample_weight is not None and tr.list_w is None)):
             # another ranking count than the captured step's (the active-learning round's
-            # second fit, run_scripts/active_PLDepth.py:182): one eager step, then capture again
+            # second fit, run_scripts/active_PLDepth.py:182), or the first sample weights: one
+            # eager step, then capture again
             tr.drop_graphs()
             self._captured = False
         tr.set_batch(x, None, None)
         tr.set_rankings(y)
+        tr.set_sample_weight(sample_weight)
         if not self._captured:
             tr.step_eager(self.optimizer.lr)
             tr.capture()
@@ -342,7 +364,9 @@ class FullyFledgedModel(object):
 
     def save(self, filepath, overwrite=True, include_optimizer=True, **kwargs):
         """keras.Model.save('... .h5') (PLDepth.py:181): model config, weights and the Adam
-        slots in Keras' HDF5 model layout; ``load_model`` (models/__init__.py) reads it back."""
+        slots in Keras' HDF5 model layout; ``load_model`` (models/__init__.py) reads it back.
+        The loss is not persisted: a loaded model is given its loss again at ``compile()``,
+        lambda weights and reduction included."""
         import os
         from ..util import keras_h5
         if not overwrite and os.path.exists(filepath):

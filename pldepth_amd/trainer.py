@@ -37,13 +37,18 @@ class ReplicaTrainer:
     def __init__(self, input_shape=(448, 448, 3), batch_size=32, ranking_size=5,
                  rankings_per_image=100, sampling_type=1, seed=0, rank=0, world_size=1,
                  process_group=None, model="ff_effnet", drop_connect=True, engine=None,
-                 gpu_sampler=True, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dp_overlap=None):
+                 gpu_sampler=True, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dp_overlap=None,
+                 rank_weights=None, reduction="mean"):
         """gpu_sampler=False: rankings come from the caller (set_rankings), as model.fit feeds
         y_true batches; otherwise the GPU sampler draws them from (gt, mask) each step.
         dp_overlap (N > 1; default from PLD_DP_OVERLAP, on): all-reduce the decoder's gradient
         buckets while the encoder's backward runs (engines with backward_decoder /
         backward_encoder and deferred weight gradients; others take the post-backward
-        exchange)."""
+        exchange).
+        rank_weights (float32 [ranking_size], a loss's lambda weights) and reduction ("mean" |
+        "sum") select the weighted ListMLE call (pld_listmle_weighted_fwd_bwd), as do sample
+        weights once set_sample_weight has been given some; at their defaults the step runs
+        pld_listmle_fwd_bwd."""
         if engine is None and model not in ENGINES:
             raise ValueError(f"unknown model {model!r} (expected one of {sorted(ENGINES)})")
         self.gpu_sampler = gpu_sampler
@@ -77,6 +82,19 @@ class ReplicaTrainer:
         self.nll = torch.empty(B * self.R_out, device=dev)
         self.loss = torch.zeros(1, device=dev)
         self.dpred = torch.empty(B, H, W, 1, device=dev)
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"reduction {reduction!r}: a training step needs 'mean' or 'sum'")
+        if reduction == "sum" and world_size > 1:
+            raise ValueError("reduction 'sum' on a data-parallel replica: the 1/world gradient "
+                             "scale would turn it into a mean over ranks")
+        self.reduction = reduction
+        self.rank_w = None
+        if rank_weights is not None:
+            rw = np.ascontiguousarray(rank_weights, dtype=np.float32).reshape(-1)
+            if rw.size != L:
+                raise ValueError(f"{rw.size} rank weights for ranking_size {L}")
+            self.rank_w = torch.from_numpy(rw).to(dev)
+        self.list_w = None  # [B * R_out] sample weights, once a step has supplied some
         # per-step scalars on the device
         self.step_dev = torch.ones(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.full((1,), 0.01, device=dev)
@@ -137,10 +155,39 @@ class ReplicaTrainer:
             self.R_out = R
             self.y_true = torch.empty(self.B, R, self.L, 2, device=self.device)
             self.nll = torch.empty(self.B * R, device=self.device)
+            if self.list_w is not None:
+                self.list_w = torch.ones(self.B * R, device=self.device)
         self._order_after_caller()
         with torch.cuda.stream(self.stream):
             self.y_true.copy_(y.reshape(self.y_true.shape))
             self._keep_alive(y)
+
+    def set_sample_weight(self, sample_weight):
+        """Per-list weights of the next step's loss (Keras sample_weight: a scalar, [N] / [N,1]
+        per list, [B] / [B,1] per image), kept in a persistent device buffer that the weighted
+        ListMLE call reads. None refills an existing buffer with ones (on the trainer's stream;
+        the captured step is unchanged) and is a no-op before any weights were given. The first weights
+        after a capture made without them need drop_graphs() first: the captured step does not
+        read the buffer."""
+        N = self.B * self.R_out
+        if sample_weight is None:
+            if self.list_w is not None:
+                with torch.cuda.stream(self.stream):
+                    self.list_w.fill_(1.0)
+            return
+        from .losses.nll_loss import check_sample_weight
+        flat, per_image = check_sample_weight(sample_weight, N, self.B)
+        w = torch.as_tensor(flat, dtype=torch.float32)
+        if per_image:
+            w = w.repeat_interleave(self.R_out)
+        if self.list_w is None:
+            if self.graphs is not None:
+                raise ValueError("sample weights given after a graph capture made without them")
+            self.list_w = torch.ones(N, device=self.device)
+        self._order_after_caller()
+        with torch.cuda.stream(self.stream):
+            self.list_w.copy_(w)
+            self._keep_alive(w)
 
     def drop_graphs(self):
         """Forget the captured step (after everything queued has run): the next step is eager,
@@ -163,8 +210,14 @@ class ReplicaTrainer:
     def _fwd_loss(self):
         eng = self.engine
         eng.forward(training=True, step=self.step_dev, image_offset=self.rank * self.B)
-        K.listmle_fwd_bwd(eng.act["pred"], self.y_true, self.B, self.R_out, self.L,
-                          dpred=self.dpred, nll=self.nll, loss=self.loss, zero_dpred=True)
+        if self.rank_w is None and self.list_w is None and self.reduction == "mean":
+            K.listmle_fwd_bwd(eng.act["pred"], self.y_true, self.B, self.R_out, self.L,
+                              dpred=self.dpred, nll=self.nll, loss=self.loss, zero_dpred=True)
+            return
+        K.listmle_weighted_fwd_bwd(eng.act["pred"], self.y_true, self.B, self.R_out, self.L,
+                                   rank_w=self.rank_w, list_w=self.list_w,
+                                   reduction=self.reduction, dpred=self.dpred, nll=self.nll,
+                                   loss=self.loss, zero_dpred=True)
 
     def _fwd_bwd(self):
         self._fwd_loss()
