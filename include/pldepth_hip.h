@@ -83,6 +83,40 @@ int pld_listmle_weighted_fwd_bwd(const float* pred, const float* y_true, int B, 
                                  float* dpred, int zero_dpred, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pairwise ranking loss over the same lists: the loss the reference's method is compared with
+ * (Chen et al. 2016; Xian et al.), built from the pieces the reference keeps for it:
+ * get_depth_relation / get_depth_relation_tf (pldepth/data/depth_utils.py:5-36), the
+ * --equality_threshold it parses, and the z0, z1 its pair tables store "to be able to compute
+ * relations with different thresholds" (pldepth/data/providers/generic_ranking_provider.py:108).
+ * With t_i = pred[b, idx_i], over the valid pairs (i before j in list order) of each list:
+ *   pair_mode      PLD_PAIRS_ALL: every i < j, L(L-1)/2 pairs; PLD_PAIRS_ADJACENT: (i, i+1), L-1
+ *                  pairs (masked samplers emit lists sorted by depth: depth neighbours)
+ *   tau            >= 0: r = get_depth_relation(z_i, z_j, tau) on float32 depths (the ratio in
+ *                  float32 against float32(1 + tau) and float32(1 / (1 + tau))); < 0: the plain
+ *                  comparison (threshold=None)
+ *   invert         r = -r (the pair provider's invert_relation_sign, ascending-depth datasets)
+ *   equal_weight   with d = t_i - t_j:
+ *                  r != 0: l = softplus(-r d), dl/dt_i = -r sigmoid(-r d) = -dl/dt_j
+ *                  r == 0: l = equal_weight d^2, dl/dt_i = 2 equal_weight d = -dl/dt_j
+ *                  loss_n = sum l / n_n over the n_n valid pairs (equal pairs count whatever
+ *                  equal_weight is); n_n = 0: loss_n = 0 and exactly 0 gradient
+ *   list_w, list_w_per_image, reduction   s_n and the reduction of pld_listmle_weighted_fwd_bwd
+ *   per_list [B*R] s_n loss_n
+ *   loss   [1]     sum_n s_n loss_n / (B*R) (PLD_REDUCE_MEAN) or the plain sum (PLD_REDUCE_SUM)
+ *   dpred  [B][HW] d loss / d pred; zeroed first when zero_dpred != 0, else added to
+ * pred, y_true and element validity (label >= 0; a pair is valid when both elements are) as
+ * pld_listmle_fwd_bwd. L may be 2..512; HW at most 2^24 (flat indices are float32). Every scalar
+ * is checked before a pointer is looked at.
+ * ------------------------------------------------------------------------------------------ */
+#define PLD_PAIRS_ALL 0
+#define PLD_PAIRS_ADJACENT 1
+int pld_pairrank_fwd_bwd(const float* pred, const float* y_true, int B, int HW, int R, int L,
+                         int pair_mode, double tau, int invert, float equal_weight,
+                         const float* list_w, int list_w_per_image, int reduction,
+                         float* per_list, float* loss, float* dpred, int zero_dpred,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer: replaces keras.optimizers.Adam(lr, amsgrad=True) (pldepth/PLDepth.py:133), i.e. TF
  * ResourceApplyAdamWithAmsgrad on every trainable variable, fused over one flat buffer:
  *   alpha = lr*sqrt(1-b2^t)/(1-b1^t); g' = grad*grad_scale; m += (g'-m)(1-b1);

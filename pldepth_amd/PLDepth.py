@@ -14,6 +14,10 @@ Differences from the reference driver, all outside the accelerated path (SURVEY 
   * ``--listmle_discount {none,log,pow2}``: position weights of the loss (p-ListMLE: rank r
     weighs 1/log2(1+r) or 2^(1-r)), passed as the loss's ``lambda_weight``; ``none`` (default)
     is the reference's plain ListMLE;
+  * ``--loss_type {nll,ranking}``: ``ranking`` trains on the pairwise ranking loss
+    (losses/ranking_loss.py) over the same sampled lists, for the listwise-versus-pairwise
+    ablation; ``--equality_threshold`` (which the reference parses and never reads) is its tau,
+    ``--pair_mode {all,adjacent}`` its pairs, ``--equal_weight`` the weight of equal pairs;
   * ``--gpus N``: data-parallel training, one process per GPU (``--batch_size`` stays the per-GPU
     batch). Started without a launcher, the command runs its N ranks as one
     ``torch.distributed.run`` child and returns that child's exit code; rank 0 prints, logs,
@@ -31,6 +35,7 @@ import numpy as np
 from .losses.losses_meta import DepthLossType
 from .losses.lambda_weights import lambda_weight_by_name
 from .losses.nll_loss import HourglassNegativeLogLikelihood
+from .losses.ranking_loss import HourglassPairwiseRankingLoss
 from .models.models_meta import ModelParameters, get_model_type_by_name
 from .models.PLDepthNet import get_pl_depth_net
 from .optimizers import Adam
@@ -82,9 +87,21 @@ def steps_per_epoch_for(ds_size, batch_size, world=1):
     return max(1, int((ds_size * 14 / 15) / (batch_size * world)))
 
 
-def build_loss(ranking_size, batch_size, listmle_discount='none'):
-    """The training loss of ``--listmle_discount``: plain ListMLE for ``none`` (the reference's
-    loss, PLDepth.py:128), else p-ListMLE with the named rank discount as its lambda weight."""
+def build_loss(ranking_size, batch_size, listmle_discount='none', loss_type='nll',
+               equality_threshold=0.03, pair_mode='all', equal_weight=1.0):
+    """The training loss of ``--loss_type``. ``nll``: plain ListMLE for ``--listmle_discount
+    none`` (the reference's loss, PLDepth.py:128), else p-ListMLE with the named rank discount as
+    its lambda weight. ``ranking``: the pairwise ranking loss over the same lists, with
+    ``--equality_threshold`` as its threshold, ``--pair_mode`` and ``--equal_weight``."""
+    if loss_type == 'ranking':
+        if listmle_discount != 'none':
+            raise ValueError("listmle_discount with the ranking loss: rank discounts belong to "
+                             "ListMLE")
+        return HourglassPairwiseRankingLoss(
+            ranking_size=ranking_size, batch_size=batch_size, threshold=equality_threshold,
+            pair_mode=pair_mode, equal_weight=equal_weight)
+    if loss_type != 'nll':
+        raise ValueError(f"unknown loss_type {loss_type!r} (expected 'nll' or 'ranking')")
     return HourglassNegativeLogLikelihood(
         ranking_size=ranking_size, batch_size=batch_size,
         lambda_weight=lambda_weight_by_name(listmle_discount, ranking_size))
@@ -125,6 +142,13 @@ def _argv(params):
               type=click.Choice(['none', 'log', 'pow2']),
               help='position weights of the ListMLE loss (p-ListMLE): rank r weighs 1/log2(1+r) '
               '(log) or 2^(1-r) (pow2); none = plain ListMLE')
+@click.option('--loss_type', default='nll', type=click.Choice(['nll', 'ranking']),
+              help='nll = ListMLE (Plackett-Luce); ranking = the pairwise ranking loss over the '
+              'same lists, with --equality_threshold as its tau')
+@click.option('--pair_mode', default='all', type=click.Choice(['all', 'adjacent']),
+              help='pairs of the ranking loss: every i < j of a list, or list neighbours')
+@click.option('--equal_weight', default=1.0, type=click.FLOAT,
+              help='weight of the squared difference on pairs the threshold calls equal')
 @click.option('--gpus', default=None, type=click.INT,
               help='data-parallel ranks, one process per GPU; --batch_size is per GPU '
               '(default: WORLD_SIZE under a launcher, else 1)')
@@ -132,6 +156,9 @@ def _argv(params):
               help='torch.distributed backend for --gpus > 1 (default: PLD_DP_BACKEND, else nccl '
               '= RCCL; gloo lets the ranks share GPUs)')
 def perform_pldepth_experiment(gpus=None, dist_backend=None, **params):
+    if params.get("loss_type") == "ranking" and params.get("listmle_discount", "none") != "none":
+        raise click.UsageError("--listmle_discount with --loss_type ranking: rank discounts "
+                               "belong to ListMLE")
     if gpus is None:  # under torch.distributed.run the launcher has said how many
         gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -162,9 +189,13 @@ def run_experiment(model_name, epochs, batch_size, seed, ranking_size, rankings_
                    initial_lr, equality_threshold, model_checkpoints, load_model_path,
                    augmentation, warmup, sampling_type, lr_multi, ds_size, input_size, data_npz,
                    save_path, log_jsonl, hr_wsi_path='', device_data=False,
-                   listmle_discount='none', rank=0, world=1):
+                   listmle_discount='none', rank=0, world=1, loss_type='nll', pair_mode='all',
+                   equal_weight=1.0):
     """One rank's run (world 1: the whole run). With world > 1 the default process group is
     initialised: compile() makes the model a data-parallel replica of it."""
+    if loss_type == 'ranking' and listmle_discount != 'none':
+        raise click.UsageError("--listmle_discount with --loss_type ranking: rank discounts "
+                               "belong to ListMLE")
     np.random.seed(seed)
     model_params = ModelParameters()
     model_params.set_parameter("model_type", get_model_type_by_name(model_name))
@@ -175,7 +206,8 @@ def run_experiment(model_name, epochs, batch_size, seed, ranking_size, rankings_
     model_params.set_parameter("batch_size", batch_size)
     model_params.set_parameter("seed", seed)
     model_params.set_parameter("equality_threshold", equality_threshold)
-    model_params.set_parameter("loss_type", DepthLossType.NLL)
+    model_params.set_parameter("loss_type", DepthLossType.RANKING if loss_type == 'ranking'
+                               else DepthLossType.NLL)
     model_params.set_parameter("augmentation", augmentation)
     model_params.set_parameter("warmup", warmup)
     if sampling_type == 0:
@@ -216,7 +248,9 @@ def run_experiment(model_name, epochs, batch_size, seed, ranking_size, rankings_
     schedule = SGDRScheduler(min_lr=initial_lr * (1 / lr_multi), max_lr=initial_lr,
                              steps_per_epoch=steps_per_epoch, lr_decay=0.9, cycle_length=epochs,
                              mult_factor=1)
-    loss_fn = build_loss(ranking_size, batch_size, listmle_discount)
+    loss_fn = build_loss(ranking_size, batch_size, listmle_discount, loss_type=loss_type,
+                         equality_threshold=equality_threshold, pair_mode=pair_mode,
+                         equal_weight=equal_weight)
     model.compile(loss=loss_fn, optimizer=Adam(learning_rate=initial_lr, amsgrad=True))
     if load_model_path:
         model.load_weights(load_model_path)

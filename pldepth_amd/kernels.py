@@ -106,6 +106,33 @@ def listmle_weighted_fwd_bwd(pred, y_true, B, R, L, rank_w=None, list_w=None,
     return loss, dpred, nll
 
 
+PAIRS = {"all": CONST["PLD_PAIRS_ALL"], "adjacent": CONST["PLD_PAIRS_ADJACENT"]}
+
+
+def pairrank_fwd_bwd(pred, y_true, B, R, L, pair_mode="all", tau=0.03, invert=False,
+                     equal_weight=1.0, list_w=None, list_w_per_image=False, reduction="mean",
+                     dpred=None, per_list=None, loss=None, zero_dpred=True):
+    """pld_pairrank_fwd_bwd: the pairwise ranking loss over the lists of y_true. pair_mode "all" |
+    "adjacent"; tau None: the plain comparison (passed as -1.0); list_w float32 [B*R], or [B] with
+    list_w_per_image (None: ones); reduction "mean" | "sum". per_list receives s_n loss_n."""
+    HW = pred.numel() // B
+    if pair_mode not in PAIRS:
+        raise ValueError(f"unknown pair_mode {pair_mode!r} (expected one of {sorted(PAIRS)})")
+    if list_w is not None and _f32(list_w).numel() != (B if list_w_per_image else B * R):
+        raise ValueError(f"list_w holds {list_w.numel()} weights, not "
+                         f"{B if list_w_per_image else B * R}")
+    dpred = torch.empty_like(pred) if dpred is None else dpred
+    per_list = torch.empty(B * R, dtype=torch.float32, device=pred.device) \
+        if per_list is None else per_list
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device) if loss is None else loss
+    lib().pld_pairrank_fwd_bwd(ptr(_f32(pred)), ptr(_f32(y_true)), B, HW, R, L, PAIRS[pair_mode],
+                               -1.0 if tau is None else float(tau), int(bool(invert)),
+                               float(equal_weight), ptr(list_w), int(bool(list_w_per_image)),
+                               REDUCE[reduction], ptr(per_list), ptr(loss), ptr(dpred),
+                               int(zero_dpred), stream())
+    return loss, dpred, per_list
+
+
 # ------------------------------------------------------------------------------- optimizer
 def adam_amsgrad(param, grad, m, v, vhat, lr, step, beta1=0.9, beta2=0.999, eps=1e-7,
                  grad_scale=1.0):

@@ -71,7 +71,10 @@ class FullyFledgedModel(object):
         The training step takes the loss's lambda weights (``loss.rank_weights``) and reduction:
         ``"none"`` is refused (a step needs a scalar), and so is ``"sum"`` at world > 1, where
         the 1/world gradient scale would turn it into a mean over ranks. A loss without those
-        attributes, or with both at their defaults, trains through the unweighted call."""
+        attributes, or with both at their defaults, trains through the unweighted call.
+        A loss whose ``kind`` attribute is ``"pairrank"`` (losses/ranking_loss.py) makes the step
+        call the pairwise ranking loss with the loss object's ``pair_args``; without the
+        attribute the step is ListMLE's."""
         from .. import dp
         from ..optimizers import Adam
         from ..trainer import ReplicaTrainer
@@ -83,6 +86,10 @@ class FullyFledgedModel(object):
             loss_kw["reduction"] = reduction
         if getattr(loss, "rank_weights", None) is not None:
             loss_kw["rank_weights"] = loss.rank_weights
+        kind = getattr(loss, "kind", "nll")
+        if kind != "nll":
+            loss_kw["loss_kind"] = kind
+            loss_kw["pair_args"] = loss.pair_args
         self.loss = loss
         self.optimizer = optimizer if optimizer is not None else Adam(amsgrad=True)
         eng = self.engine
@@ -391,7 +398,7 @@ class EffNetFullyFledged(FullyFledgedModel):
         laid out for (Keras builds for a dynamic batch; the reference always trains with a
         fixed one, PLDepth.py:31,129)."""
         from .effnet_ff import EffNetFF
-        if loss_type != DepthLossType.NLL:
+        if loss_type not in (DepthLossType.NLL, DepthLossType.RANKING):  # the same network
             raise ValueError(f"unsupported loss type {loss_type}")
         eng = EffNetFF(tuple(input_shape), batch_size, seed=seed)
         return EffNetFullyFledged(eng, batch_size=batch_size), preprocess_input_effnet

@@ -18,7 +18,7 @@ class ReDWebNetTFVersion(FullyFledgedModel):
     def get_model_and_normalization(input_shape, ranking_size, loss_type=DepthLossType.NLL,
                                     batch_size=4, seed=0):
         from .redweb_ff import RedWebFF
-        if loss_type != DepthLossType.NLL:
+        if loss_type not in (DepthLossType.NLL, DepthLossType.RANKING):  # the same network
             raise ValueError(f"unsupported loss type {loss_type}")
         eng = RedWebFF(tuple(input_shape), batch_size, seed=seed)
         return ReDWebNetTFVersion(eng, batch_size=batch_size), preprocess_input

@@ -38,7 +38,7 @@ class ReplicaTrainer:
                  rankings_per_image=100, sampling_type=1, seed=0, rank=0, world_size=1,
                  process_group=None, model="ff_effnet", drop_connect=True, engine=None,
                  gpu_sampler=True, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dp_overlap=None,
-                 rank_weights=None, reduction="mean"):
+                 rank_weights=None, reduction="mean", loss_kind="nll", pair_args=None):
         """gpu_sampler=False: rankings come from the caller (set_rankings), as model.fit feeds
         y_true batches; otherwise the GPU sampler draws them from (gt, mask) each step.
         dp_overlap (N > 1; default from PLD_DP_OVERLAP, on): all-reduce the decoder's gradient
@@ -48,9 +48,21 @@ class ReplicaTrainer:
         rank_weights (float32 [ranking_size], a loss's lambda weights) and reduction ("mean" |
         "sum") select the weighted ListMLE call (pld_listmle_weighted_fwd_bwd), as do sample
         weights once set_sample_weight has been given some; at their defaults the step runs
-        pld_listmle_fwd_bwd."""
+        pld_listmle_fwd_bwd.
+        loss_kind "pairrank" trains on the pairwise ranking loss instead (pld_pairrank_fwd_bwd
+        with pair_args: pair_mode, tau, invert, equal_weight), into the same dpred, nll and loss
+        buffers; sample weights and reduction apply as above, rank weights do not exist there."""
         if engine is None and model not in ENGINES:
             raise ValueError(f"unknown model {model!r} (expected one of {sorted(ENGINES)})")
+        if loss_kind not in ("nll", "pairrank"):
+            raise ValueError(f"unknown loss_kind {loss_kind!r} (expected 'nll' or 'pairrank')")
+        if loss_kind == "pairrank" and rank_weights is not None:
+            raise ValueError("rank_weights with loss_kind 'pairrank': rank discounts belong to "
+                             "ListMLE")
+        if loss_kind == "nll" and pair_args is not None:
+            raise ValueError("pair_args with loss_kind 'nll'")
+        self.loss_kind = loss_kind
+        self.pair_args = dict(pair_args or {})
         self.gpu_sampler = gpu_sampler
         self.betas = (beta_1, beta_2, epsilon)
         self.B, self.L, self.R = batch_size, ranking_size, rankings_per_image
@@ -210,6 +222,12 @@ class ReplicaTrainer:
     def _fwd_loss(self):
         eng = self.engine
         eng.forward(training=True, step=self.step_dev, image_offset=self.rank * self.B)
+        if self.loss_kind == "pairrank":
+            K.pairrank_fwd_bwd(eng.act["pred"], self.y_true, self.B, self.R_out, self.L,
+                               list_w=self.list_w, reduction=self.reduction, dpred=self.dpred,
+                               per_list=self.nll, loss=self.loss, zero_dpred=True,
+                               **self.pair_args)
+            return
         if self.rank_w is None and self.list_w is None and self.reduction == "mean":
             K.listmle_fwd_bwd(eng.act["pred"], self.y_true, self.B, self.R_out, self.L,
                               dpred=self.dpred, nll=self.nll, loss=self.loss, zero_dpred=True)

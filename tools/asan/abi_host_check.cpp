@@ -6,6 +6,7 @@
 // eligibility helpers — and the argument checks of the compute entries (NULL / inconsistent
 // arguments must come back as PLD_ERR_ARG with a message, before any device work). No GPU is
 // needed; kernels are never launched. Exit 0 and "asan host check OK" on success.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -174,6 +175,39 @@ int main() {
     EXPECT(pld_al_oracle(gt, 1, 2, 2, tab, 40, PLD_ORACLE_MAX_L + 1, 2, y, nullptr) ==
            PLD_ERR_UNSUPPORTED);
     EXPECT(pld_al_oracle(gt, 1, 2, 2, tab, 4, 0, 2, y, nullptr) == PLD_ERR_ARG);
+  }
+
+  // pairwise ranking loss: every scalar is refused before a pointer is looked at (all pointers
+  // null here), then the null pointers and dpred's alignment; nothing is launched
+  {
+    const float nanf = std::nanf(""), inff = HUGE_VALF;
+    const double nan = std::nan(""), inf = HUGE_VAL;
+    auto call = [](int HW, int L, int mode, double tau, float ew, int red, float* p,
+                   float* dpred) {
+      return pld_pairrank_fwd_bwd(p, p, 1, HW, 1, L, mode, tau, 0, ew, nullptr, 0, red, p, p,
+                                  dpred, 1, nullptr);
+    };
+    auto refused = [](int rc, const char* what) {
+      return rc == PLD_ERR_ARG && std::strstr(pld_last_error(), what) != nullptr;
+    };
+    const int all = PLD_PAIRS_ALL, mean = PLD_REDUCE_MEAN;
+    for (int L : {1, 0, -3, 513})
+      EXPECT(refused(call(4, L, all, 0.03, 1.f, mean, nullptr, nullptr), "L must be 2..512"));
+    EXPECT(refused(call(0, 3, all, 0.03, 1.f, mean, nullptr, nullptr), "bad shape"));
+    EXPECT(refused(call((1 << 24) + 1, 3, all, 0.03, 1.f, mean, nullptr, nullptr), "2^24"));
+    for (int mode : {-1, 2})
+      EXPECT(refused(call(4, 3, mode, 0.03, 1.f, mean, nullptr, nullptr), "unknown pair_mode"));
+    for (int red : {-1, 2})
+      EXPECT(refused(call(4, 3, all, 0.03, 1.f, red, nullptr, nullptr), "unknown reduction"));
+    for (double tau : {nan, inf, -inf})
+      EXPECT(refused(call(4, 3, all, tau, 1.f, mean, nullptr, nullptr), "tau must be finite"));
+    for (float ew : {nanf, inff, -0.5f})
+      EXPECT(refused(call(4, 3, all, 0.03, ew, mean, nullptr, nullptr), "equal_weight"));
+    EXPECT(refused(call(4, 3, all, 0.03, 1.f, mean, nullptr, nullptr), "null pointer"));
+    EXPECT(refused(call(1 << 24, 512, PLD_PAIRS_ADJACENT, -1.0, 0.f, PLD_REDUCE_SUM, nullptr,
+                        nullptr), "null pointer"));  // every scalar at its limit passes
+    float buf[8] __attribute__((aligned(16))) = {0};
+    EXPECT(refused(call(4, 3, all, 0.03, 1.f, mean, buf, buf + 1), "16-byte aligned"));
   }
 
   if (failures) {
