@@ -345,6 +345,23 @@ int pld_pgemm_bn_bwd(const float* x, const float* dy, int64_t rows, int k, const
                      const float* k12, const float* w, int n, float* y, int accumulate,
                      void* stream);
 
+/* The same two folds for the deep-K blocks on bf16x3 MFMA (csrc/pgemm_x3.hip): K % 16 == 0,
+ * K <= 1152, N % 4 == 0, N <= 320; every operand 16-byte aligned. w_split is the
+ * pld_filter_split copy of w [N][K] (w_nat's for the project conv, w_dg's for the expand
+ * dgrad). The staged operand is bit for bit what pld_bn_apply / pld_bn_bwd write; the product
+ * has the bf16x3 convs' arithmetic. pld_pgemm_x3_ok is a status like every other call: PLD_OK
+ * where the two kernels take the shape, PLD_ERR_ARG (the reason in pld_last_error) where not;
+ * such a shape is an error in the kernels too, never another kernel. */
+int pld_pgemm_x3_ok(int k, int n);
+int pld_pgemm_x3_bn_act(const float* x, int64_t rows, int k, const float* mean,
+                        const float* invstd, const float* gamma, const float* beta, int act,
+                        const float* gate, int hw, const void* w_split, int n, float* y,
+                        int accumulate, void* stream);
+int pld_pgemm_x3_bn_bwd(const float* x, const float* dy, int64_t rows, int k, const float* mean,
+                        const float* invstd, const float* gamma, const float* beta, int act,
+                        const float* k12, const void* w_split, int n, float* y, int accumulate,
+                        void* stream);
+
 /* residual forms (ResNet-50 blocks `Add -> ReLU`, keras resnet block1; ReDWeb
  * BottleneckConvLayer `out += residual; relu` redweb.py:137-165 and FeatureFusionLayer
  * `x_left + x_up` redweb.py:270):  y = act(bn(x) + res);  backward: dz = dy*act'(bn(x)+res),

@@ -11,7 +11,7 @@ import numpy as np
 
 import torch
 
-from ._lib import CONST, ConvArgs, RefreshDesc as _RefreshDesc, lib
+from ._lib import CONST, ConvArgs, PLDError, RefreshDesc as _RefreshDesc, lib
 
 # selectors and limits of the C ABI, by their names in include/pldepth_hip.h
 ACT = {k: CONST["PLD_ACT_" + v] for k, v in {
@@ -726,6 +726,76 @@ def pgemm_bn_bwd(x, dy, rows, k, mean, invstd, gamma, beta, act, k12, w, n, y,
     lib().pld_pgemm_bn_bwd(ptr(x), ptr(dy), rows, k, ptr(mean), ptr(invstd), ptr(gamma),
                            ptr(beta), ACT[act], ptr(k12), ptr(w), n, ptr(y), int(accumulate),
                            stream())
+
+
+def pgemm_x3_ok(k, n):
+    """Whether pgemm_x3_bn_act / pgemm_x3_bn_bwd take a [rows, k] x [n, k] product
+    (pld_pgemm_x3_ok answers with a status)."""
+    try:
+        lib().pld_pgemm_x3_ok(int(k), int(n))
+    except PLDError:
+        return False
+    return True
+
+
+def pgemm_x3_pays(k, n, rows):
+    """Where the fused bf16x3 pgemm (csrc/pgemm_x3.hip) is wired in place of the unfused pair
+    (bn_apply + conv2d_fwd, or bn_bwd's apply + conv2d_dgrad), per shape of the 448^2 batch-32
+    model: the deep-K blocks pgemm_pays leaves to the MFMA tiles. Measured with
+    tools/pgemm_micro.py --family x3 on MI355X (profiles/r08_pgemm_x3_micro.txt; us per call,
+    graph-replayed, median of 20, +- = largest difference between two replays; the expand
+    dgrads with bn_bwd_coeffs on the fused side and the whole bn_bwd on the other):
+
+        shape         rows    K     N    fused        pair        saved
+        3a_proj      100352   144   40   34.0 +-2.6   49.6 +-3.1   15.5   wired
+        3b_proj      100352   240   40   45.9 +-1.6   67.9 +-10.   22.1   wired
+        4a_proj       25088   240   80   14.9 +-0.8   33.1 +-1.7   18.1   wired
+        4bc_proj      25088   480   80   25.6 +-3.5   43.8 +-2.6   18.2   wired
+        5a_proj       25088   480  112   28.2 +-3.3   44.2 +-3.7   15.9   wired
+        5bc_proj      25088   672  112   34.3 +-3.1   52.5 +-5.7   18.2   wired
+        6a_proj        6272   672  192   24.1 +-1.3   34.3 +-8.4   10.1   wired
+        6bcd_proj      6272  1152  192   40.4 +-1.2   44.5 +-2.6    4.1   inside the spread
+        7a_proj        6272  1152  320   59.1 +-3.2   44.8 +-7.0  -14.4   loses
+        3b4a_exdg    100352   240   40   97.1 +-1.8  121.9 +-4.1   24.8   wired
+        4bc5a_exdg    25088   480   80   55.9 +-1.5   73.1 +-9.6   17.1   wired
+        5bc6a_exdg    25088   672  112   76.2 +-1.9   96.2 +-8.6   20.0   wired
+        6bcd7a_exdg    6272  1152  192   61.4 +-1.0   61.7 +-8.6    0.3   a tie
+
+    At 14 x 14 with K = 1152 the bf16x3 MFMA work of a 32-row strip is as long as its operand
+    stream and 196 workgroups do not fill 256 CUs: those stay on the im2col tiles."""
+    if not pgemm_x3_ok(k, n) or pgemm_pays(k, n):
+        return False
+    return (int(k), int(n), int(rows)) in PGEMM_X3_PAYS
+
+
+# (K, N, rows) of the "wired" lines above (a project conv and an expand dgrad of one shape share
+# a key and a verdict)
+PGEMM_X3_PAYS = frozenset([(144, 40, 100352), (240, 40, 100352), (240, 80, 25088),
+                           (480, 80, 25088), (480, 112, 25088), (672, 112, 25088),
+                           (672, 192, 6272)])
+
+
+def _split_of(w):
+    s = getattr(w, "_pld_split", None)
+    if s is None:
+        raise PLDError("pgemm_x3: the filter has no split copy (filter_split / filter_refresh)")
+    return s
+
+
+def pgemm_x3_bn_act(x, rows, k, mean, invstd, gamma, beta, act, w, n, y, gate=None, hw=0,
+                    accumulate=False):
+    """pgemm_bn_act on bf16x3 MFMA; w [n][k] carries its pld_filter_split copy (w._pld_split)."""
+    lib().pld_pgemm_x3_bn_act(ptr(x), rows, k, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
+                              ACT[act], ptr(gate), hw, ptr(_split_of(w)), n, ptr(y),
+                              int(accumulate), stream())
+
+
+def pgemm_x3_bn_bwd(x, dy, rows, k, mean, invstd, gamma, beta, act, k12, w, n, y,
+                    accumulate=False):
+    """pgemm_bn_bwd on bf16x3 MFMA; w [n][k] carries its pld_filter_split copy."""
+    lib().pld_pgemm_x3_bn_bwd(ptr(x), ptr(dy), rows, k, ptr(mean), ptr(invstd), ptr(gamma),
+                              ptr(beta), ACT[act], ptr(k12), ptr(_split_of(w)), n, ptr(y),
+                              int(accumulate), stream())
 
 
 def bn_add_apply(x, rows, c, mean, invstd, gamma, beta, res, act, y):

@@ -116,6 +116,11 @@ class EffNetFF:
         self.init_weights(seed)
         # thin-N 1x1 convs with the neighbouring BN (+ act, SE gate) folded in (pgemm.hip)
         self.fuse_pgemm = True
+        # the same folds for the deep-K blocks on bf16x3 MFMA (csrc/pgemm_x3.hip), taken where
+        # fuse_pgemm is on and the conv's math resolves to bf16x3. "1": per shape where
+        # kernels.pgemm_x3_pays measured a gain; "0": off; "all": every eligible block (A/B
+        # runs, parity tests at sizes the table does not hold). Read at every step.
+        self.fuse_pgemm_x3 = os.environ.get("PLD_PGEMM_X3", "1")
         self._alloc_activations()
         self.drop_connect = True
         self.seed = seed
@@ -338,6 +343,15 @@ class EffNetFF:
             self._k12[(c, slot)] = torch.empty(2 * c, device=self.device)
         return self._k12[(c, slot)]
 
+    def _x3_fuse(self, blk, k, n, h, w):
+        """Whether a 1x1 conv [B h w, k] -> n of `blk` with a BN-side elementwise op in front of
+        it takes pgemm_x3 (self.fuse_pgemm_x3)."""
+        mode = self.fuse_pgemm_x3
+        if (mode == "0" or not self.fuse_pgemm or self._em(h, w) != "bf16x3"
+                or K.pgemm_pays(k, n) or not K.pgemm_x3_ok(k, n)):
+            return False
+        return mode == "all" or K.pgemm_x3_pays(k, n, self.B * h * w)
+
     def _dw_dgrad_fuse(self, blk):
         """(pro, epi): the BN-backward stages the block's depthwise dgrad takes on
         (self.fuse_dw_dgrad); stride-1 blocks the LDS-tiled kernel runs only."""
@@ -474,7 +488,15 @@ class EffNetFF:
         se_w = (F[blk["se_w1"]].view(blk["cexp"], blk["cse"]), F[blk["se_b1"]],
                 F[blk["se_w2"]].view(blk["cse"], blk["cexp"]), F[blk["se_b2"]])
         pg = training and blk["fused_project"]
-        if pg:
+        px = training and not pg and self._x3_fuse(blk, blk["cexp"], blk["cout"], oh, ow)
+        if px:
+            # as below on bf16x3 MFMA (pgemm_x3): the deep-K blocks, se_excite is not written
+            K.se_fwd(A[n + "dw_pre"], *se_w, blk["pooled"], blk["z1"], blk["gate"],
+                     bn=(bn.mean, bn.invstd, bn.gamma, bn.beta), act="swish")
+            K.pgemm_x3_bn_act(A[n + "dw_pre"], rows, blk["cexp"], bn.mean, bn.invstd, bn.gamma,
+                              bn.beta, "swish", blk["project"].w_nat, blk["cout"],
+                              A[n + "project_pre"], gate=blk["gate"], hw=oh * ow)
+        elif pg:
             # the SE squeeze applies BN + swish to dw_pre on the fly, and the project conv reads
             # dw_pre through BN + swish + the SE gate (pgemm): neither the block's activation
             # nor se_excite is materialised
@@ -496,7 +518,7 @@ class EffNetFF:
                 K.se_fwd(A[n + "activation"], *se_w, blk["pooled"], blk["z1"], blk["gate"])
                 self._gate_mul(A[n + "activation"], blk["gate"], A[n + "se_excite"])
         pbn = blk["project_bn"]
-        if pg:
+        if pg or px:
             pbn.stats_(A[n + "project_pre"], rows, training)
         else:
             pbn.conv_fwd_stats(K.conv_args(A[n + "se_excite"], None, 1, 1, 1, 0, 0, oh, ow,
@@ -700,8 +722,12 @@ class EffNetFF:
             k12 = self._k12_buf(blk["cexp"])
             # epi: the expand BN's backward sums (dgamma, dbeta, k12) come from the dgrad's
             # epilogue, and its elementwise pass (gpe), where no pgemm folds it in, follows
+            # (pgemm on exact fp32 FMAs for the early blocks, pgemm_x3 on bf16x3 MFMA beyond)
+            xd = (not blk["fused_expand_dgrad"]
+                  and self._x3_fuse(blk, blk["cexp"], blk["cin"], h, w))
+            fused = blk["fused_expand_dgrad"] or xd
             gpe = None
-            if not blk["fused_expand_dgrad"]:
+            if not fused:
                 gpe = self._gpre_buf(A[n + "expand_pre"].shape)
             if pro:
                 K.dwconv_dgrad_se_bn(gse, A[n + "dw_pre"], bnv, bk12, blk["gate"], blk["addn"],
@@ -718,12 +744,13 @@ class EffNetFF:
                                accumulate=is_tap)
             # residual: gx_in is gy's buffer (_alloc_activations) and already holds gy
             res = blk["residual"]
-            if blk["fused_expand_dgrad"]:
+            if fused:
                 if not epi:
                     K.bn_bwd_coeffs(A[n + "expand_pre"], ge, B * h * w, blk["cexp"], *bnp,
                                     "swish", ebn.dgamma, ebn.dbeta, k12)
-                K.pgemm_bn_bwd(A[n + "expand_pre"], ge, B * h * w, blk["cexp"], *bnp, "swish",
-                               k12, blk["expand"].w_dg, blk["cin"], gx_in, accumulate=res)
+                call = K.pgemm_x3_bn_bwd if xd else K.pgemm_bn_bwd
+                call(A[n + "expand_pre"], ge, B * h * w, blk["cexp"], *bnp, "swish", k12,
+                     blk["expand"].w_dg, blk["cin"], gx_in, accumulate=res)
             else:
                 if not epi:
                     ebn.bwd(A[n + "expand_pre"], ge, B * h * w, "swish", gpe)
